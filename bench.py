@@ -52,6 +52,7 @@ MFMA_PER_TILE = {"f32": {"conv_fwd": (103, 0), "conv_bwd": (230, 0)}, "bf16": {"
 MAC_PER_EDGE = {"conv_fwd": 3669, "conv_bwd": 3 * 2543}
 PEAK_BF16_MFMA_TFLOPS = 2500.0  # MI355X_MICROARCH.md: ~2.5 PF dense bf16 (the K=32 forms; the K=16 form used here is half of it)
 MATRIX_PIPE_CYCLES_PER_US = 1024 * 2400.0       # 1,024 SIMDs at 2.4 GHz
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: total size of the written arrays
 
 
 def parse():
@@ -116,7 +117,13 @@ def parse():
     ap.add_argument("--epoch-steps", type=int, default=329, help="batches in the epoch leg (Davis: 21,039 train pairs / 64)")
     ap.add_argument("--cpu-runs", type=int, default=20, help="timed CPU-baseline runs per thread count (median)")
     ap.add_argument("--cpu-pairs", type=int, default=0, help="pairs in the CPU sample (0 = choose for ~10-30 s)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy in "
+                         "float32: the encoder outputs and every gradient the step returns (or the affinities, --scope joint "
+                         "forward); a seeded row sample once the arrays pass %d MB" % (DUMP_LIMIT_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     wl, dt = {2: ("davis_b64", "f32"), 3: ("kiba_b32", "f32"), 4: ("long_graph_x64", "f32"), 5: ("bindingdb_b32_44", "bf16")}[args.config]
     args.workload = args.workload or wl
     args.dtype = args.dtype or dt
@@ -130,6 +137,32 @@ def kernel_source_digest():
         if f.endswith((".hip", ".h")):
             h.update(open(os.path.join(d, f), "rb").read())
     return h.hexdigest()[:16]
+
+
+def host_outputs(named):
+    """{name: float32 numpy copy} of a step's device outputs (bf16 widened; None entries dropped)."""
+    return {k: v.detach().float().cpu().numpy() for k, v in named.items() if v is not None}
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write {name: float32 array} as out_dir/<name>.npy.  Above `limit` bytes in all, every array with more than one
+    row keeps the same fixed, seeded sample of its rows (sorted), and <name>.rows.npy (float64) says which."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        keep = 0.9 * limit / total                   # headroom for the row-index files
+        for k in sorted(arrays):
+            a = arrays[k]
+            if a.ndim == 0 or a.shape[0] < 2:
+                continue
+            n = max(1, int(a.shape[0] * keep))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], n, replace=False))
+            arrays[k] = np.ascontiguousarray(a[rows])
+            arrays[k + ".rows"] = rows.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return sorted(arrays)
 
 
 def measured_copy_gbs(dev, nbytes=1 << 30, reps=5):
@@ -251,6 +284,9 @@ def main():
     dropout_on = train and not args.eval_mode
     convs = wl.get("convs", 2)
     model, state = entry._load_model(dev, num_convs=convs)
+    # the kernels' dropout {seed, offset} is drawn from torch's CUDA generator, whose start seed is not fixed: seeded, so
+    # that the same arguments compute the same steps (--dump-outputs compares runs and builds output for output)
+    torch.manual_seed(1234 + rank)
     model.train(dropout_on)
     lengths = ds.real_lengths(wl["lengths"], wl["pairs"], seed=1000 + rank) if "lengths" in wl else None
     pb, mb = ds.pair_batch(wl["pairs"], seed=rank, length=wl.get("length", 300), thresh=wl["thresh"],
@@ -292,6 +328,8 @@ def main():
     prot_params = [p for p in model.protein_gnn.parameters() if p.numel()]
     drug_params = [p for p in model.molecule_gnn.parameters() if p.numel()]
     enc_params = prot_params + drug_params
+    prot_names = ["protein_gnn." + n for n, p in model.protein_gnn.named_parameters() if p.numel()]
+    drug_names = ["molecule_gnn." + n for n, p in model.molecule_gnn.named_parameters() if p.numel()]
     n_enc = sum(p.numel() for p in enc_params)
     for p in model.parameters():
         p.requires_grad_(train)
@@ -307,6 +345,10 @@ def main():
     pair_all = torch.empty(wl["pairs"] * world, 512, device=dev)
     grad_bucket = torch.zeros(n_enc, device=dev)
     all_params = [p for p in model.parameters() if p.numel()]
+    all_names = [n for n, p in model.named_parameters() if p.numel()]
+    # forward outputs of the latest step (eager) / of the captured step (graph) for --dump-outputs; detached aliases, as
+    # a step's autograd graph kept alive into the next one breaks its capture
+    fwd_out = {}
     pre_ids = {id(p) for p in model.pre_gather_parameters()}
     pre_idx = [i for i, p in enumerate(all_params) if id(p) in pre_ids]      # rank-local gradients under pair parallelism
     joint_bucket = torch.zeros(sum(all_params[i].numel() for i in pre_idx), device=dev)
@@ -320,9 +362,11 @@ def main():
         main_s = torch.cuda.current_stream()
         if args.only == "protein":                    # diagnostic: one encoder alone
             residues = model.protein_gnn(**pdata)
+            fwd_out["residues"] = residues.detach()
             return torch.autograd.grad([residues], prot_params, [g_res]) if train else residues
         if args.only == "drug":
             atoms = model.molecule_gnn(**mdata)
+            fwd_out["atoms"] = atoms.detach()
             return torch.autograd.grad([atoms], drug_params, [g_atm]) if train else atoms
         side.wait_stream(main_s)
         # the protein chain is the critical path: it is issued first and stays on the launch stream (a HIP graph keeps
@@ -339,6 +383,7 @@ def main():
         residues = model.protein_gnn(**pdata)
         if args.issue_order != "drug":
             atoms = drug_forward()
+        fwd_out["residues"], fwd_out["atoms"] = residues.detach(), atoms.detach()
         if not train:
             main_s.wait_stream(side)
             return residues, atoms
@@ -369,6 +414,7 @@ def main():
             pred = pred.float()
         else:
             pred, _ = jmodel(jp, jm)
+        fwd_out["affinity"] = pred.detach()
         if not train:
             return pred
         loss = torch.nn.functional.mse_loss(pred, target[:pred.shape[0]])
@@ -377,6 +423,21 @@ def main():
         return torch.autograd.grad(loss, all_params)
 
     step = encoders_step if args.scope == "encoders" else joint_step
+    grad_names = all_names if args.scope == "joint" else {"protein": prot_names, "drug": drug_names}.get(
+        args.only, prot_names + drug_names)
+
+    def named_outputs(o):
+        """What a caller of the step receives, by name: forward outputs, then the weight gradients (training), then
+        the results of the data-parallel collectives when they ran."""
+        named = dict(fwd_out)
+        if train:
+            named.update(("grad." + n, g) for n, g in zip(grad_names, o))
+        if collectives and not rehearsal:
+            if args.scope == "encoders":
+                named["allgathered_pair_embeddings"] = pair_all
+            if train:
+                named["allreduced_gradients"] = grad_bucket if args.scope == "encoders" else joint_bucket
+        return named
 
     def comm(out):
         """The per-step collectives of data-parallel training (issued eagerly after the compute of the step)."""
@@ -434,6 +495,7 @@ def main():
             else:
                 o = step()
             comm(o)
+            return o
 
         def barrier():
             if world > 1:
@@ -447,9 +509,13 @@ def main():
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            run()
+            last = run()
         barrier()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:       # host copies now: the legs below run eager steps over fwd_out
+            names = dump_outputs(args.dump_outputs, host_outputs(named_outputs(last)))
+            print(f"bench.py: wrote {len(names)} arrays of the last timed step to {args.dump_outputs}",
+                  file=sys.stderr, flush=True)
         if world > 1:
             t = torch.tensor([dt], device="cpu" if rehearsal else dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)

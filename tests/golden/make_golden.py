@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/*.npz from the reference itself.  Runs ONLY in the
-build container (needs /root/reference); the GPU box and the test-suite only
-read the .npz files this writes.  Nothing from the reference is copied: the
+"""Generate tests/golden/*.npz from the reference itself.  Runs ONLY where a
+checkout of the upstream CASTER-DTA repository is at hand ($CASTER_DTA_REFERENCE
+names it); the GPU box and the test-suite only read the .npz files this writes.
+`--out-dir DIR --check` regenerates into DIR and compares the result bit for bit
+with the committed fixtures (exit status 1 on any difference).  Nothing from the reference is copied: the
 fixtures are numbers (inputs, weights-as-data, expected outputs, gradients).
 
 How the reference is driven
 ---------------------------
 ``models/gvp_layers.py`` and ``models/protein_gnn.py`` are imported unmodified
-from /root/reference.  Three modules they import are not installed here and are
+from $CASTER_DTA_REFERENCE.  Three modules they import are not installed here and are
 replaced by minimal stand-ins registered in ``sys.modules`` *before* the import:
 
 * ``torch_geometric.nn.MessagePassing``: base class of ``GVPConv``.  The stand-in
@@ -39,9 +41,12 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
-REF = "/root/reference"
+REF = os.path.abspath(os.environ["CASTER_DTA_REFERENCE"]) if os.environ.get("CASTER_DTA_REFERENCE") else None
 sys.dont_write_bytecode = True
-OUT = HERE          # --out-dir overrides (the CPU test-suite regenerates into a temp dir and compares)
+OUT = HERE          # --out-dir overrides (--check regenerates into another directory and compares)
+FIXTURES = {"state": "pretrained_state.npz", "lba_small": "lba_small.npz", "lba_sparse": "lba_sparse.npz",
+            "gvp_units": "gvp_units.npz", "gvp_stacks": "gvp_stacks.npz", "edge_feats": "edge_feats.npz",
+            "lba_amp_bf16": "lba_amp_bf16.npz"}
 
 
 def _load_by_path(name, path):
@@ -265,11 +270,16 @@ def main():
     global OUT
     ap = argparse.ArgumentParser()
     ap.add_argument("--out-dir", default=HERE)
-    ap.add_argument("--only", default=None, help="comma-separated subset of {state,lba_small,lba_sparse,gvp_units,gvp_stacks,edge_feats,lba_amp_bf16}")
+    ap.add_argument("--only", default=None, help="comma-separated subset of {%s}" % ",".join(FIXTURES))
+    ap.add_argument("--check", action="store_true",
+                    help="compare the regenerated files bit for bit with the committed fixtures (needs --out-dir elsewhere)")
     args = ap.parse_args()
+    if REF is None or not os.path.isdir(os.path.join(REF, "models")):
+        ap.error("set CASTER_DTA_REFERENCE to a checkout of the upstream CASTER-DTA repository")
     OUT = args.out_dir
-    want = set(args.only.split(",")) if args.only else {"state", "lba_small", "lba_sparse", "gvp_units", "gvp_stacks",
-                                                           "edge_feats", "lba_amp_bf16"}
+    if args.check and os.path.abspath(OUT) == HERE:
+        ap.error("--check compares against the committed fixtures: give --out-dir another directory")
+    want = set(args.only.split(",")) if args.only else set(FIXTURES)
     os.makedirs(OUT, exist_ok=True)
     install_standins()
     assert not any(os.path.abspath(p or ".").startswith(os.path.join(REPO, "caster-dta_amd")) for p in sys.path), \
@@ -330,7 +340,7 @@ def main():
     if "gvp_stacks" in want:
         gvp_stacks(SelectableProteinModelWrapper)
     if "gvp_units" not in want:
-        return
+        return finish(args, want)
 
     # ---- (1)/(2): standalone GVP / LayerNorm instances, every dim signature of the path ----
     import torch.nn.functional as F
@@ -415,6 +425,27 @@ def main():
               eattr=(es64[perm], ev64[perm]))
     print("fp64 rotation delta", float((rot - out64).abs().max()),
           "edge-permutation delta", float((prm - out64).abs().max()))
+    finish(args, want)
+
+
+def finish(args, want):
+    if args.check:
+        bad = check_fixtures([FIXTURES[k] for k in sorted(want)])
+        print("check:", "every regenerated fixture matches bit for bit" if not bad else "DIFFERENT: " + ", ".join(bad))
+        if bad:
+            sys.exit(1)
+
+
+def check_fixtures(names):
+    """Names of the fixtures in OUT that differ from the committed ones (keys, dtypes, shapes or bytes)."""
+    bad = []
+    for name in names:
+        new, old = np.load(os.path.join(OUT, name)), np.load(os.path.join(HERE, name))
+        if set(new.files) != set(old.files) or any(
+                new[k].dtype != old[k].dtype or new[k].shape != old[k].shape or new[k].tobytes() != old[k].tobytes()
+                for k in old.files):
+            bad.append(name)
+    return bad
 
 
 if __name__ == "__main__":

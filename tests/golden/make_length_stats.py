@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """Sequence LENGTHS of the Davis / KIBA proteins the reference ships
-(/root/reference/data/deepdta_data/{davis,kiba}/proteins.txt: JSON maps id -> sequence).  Only the integer
+($CASTER_DTA_REFERENCE/data/deepdta_data/{davis,kiba}/proteins.txt: JSON maps id -> sequence).  Only the integer
 lengths are written (tests/golden/protein_lengths.json): they size the "real-length" synthetic batches
-(BASELINE config 3 = KIBA, 32 pairs per GPU).  Runs only in the build container."""
+(BASELINE config 3 = KIBA, 32 pairs per GPU).  Runs only where a checkout of the upstream repository is at hand."""
 import json
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = "/root/reference/data/deepdta_data"
+REF = os.path.join(os.environ.get("CASTER_DTA_REFERENCE", ""), "data", "deepdta_data")
 
 
 def main():

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """CPU time of the oracle (oracle/gvp_oracle.py, the `cpu_baseline` of bench.py) against the UNMODIFIED reference protein
 encoder on the same batch ("the restatement/reference time ratio is known").  Runs only in the build container
-(needs /root/reference; same stand-ins as make_golden.py); prints one line for BASELINE.md."""
+(needs $CASTER_DTA_REFERENCE as make_golden.py does; same stand-ins); prints one line for BASELINE.md."""
 import importlib.util, json, os, statistics, sys, time
 import numpy as np
 import torch
@@ -10,6 +10,7 @@ REPO = os.path.dirname(os.path.dirname(HERE))
 spec = importlib.util.spec_from_file_location("make_golden", os.path.join(HERE, "make_golden.py"))
 mg = importlib.util.module_from_spec(spec)
 spec.loader.exec_module(mg)
+assert mg.REF, "set CASTER_DTA_REFERENCE to a checkout of the upstream CASTER-DTA repository"
 mg.install_standins()
 sys.path.insert(0, mg.REF)
 from models.protein_gnn import SelectableProteinModelWrapper          # the reference

@@ -67,3 +67,33 @@ def test_bench_rejects_a_world_size_that_contradicts_gpus():
     env = dict(os.environ, WORLD_SIZE="4", RANK="0", LOCAL_RANK="0", BENCH_DRY_RUN="1")
     out = subprocess.run([sys.executable, path, "--gpus", "2"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode != 0 and "WORLD_SIZE=4" in out.stderr
+
+
+def test_bench_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    """--dump-outputs: every array lands as <name>.npy; past the size limit each multi-row array keeps the same seeded
+    row sample on every call, with the row indices beside it, and the files stay within the limit."""
+    bench, _ = _bench_module()
+    rng = np.random.default_rng(3)
+    arrays = {"residues": rng.normal(size=(4000, 64)).astype(np.float32), "grad.w": rng.normal(size=(7,)).astype(np.float32),
+              "scalar": np.float32(2.5) * np.ones((), np.float32)}
+    names = bench.dump_outputs(str(tmp_path / "all"), dict(arrays))
+    assert names == sorted(arrays)
+    for k, a in arrays.items():
+        assert np.array_equal(np.load(tmp_path / "all" / f"{k}.npy"), a)
+
+    limit = 256 << 10
+    runs = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        bench.dump_outputs(str(d), dict(arrays), limit=limit)
+        files = sorted(p.name for p in d.iterdir())
+        assert sum((d / f).stat().st_size for f in files) <= limit
+        got = {f[:-4]: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+        runs.append(got)
+    a, b = runs
+    assert sorted(a) == ["grad.w", "grad.w.rows", "residues", "residues.rows", "scalar"]
+    rows = a["residues.rows"].astype(np.int64)
+    assert len(rows) < 4000 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(a["residues"], arrays["residues"][rows])
+    assert all(np.array_equal(a[k], b[k]) for k in a)
