@@ -94,6 +94,9 @@ struct GineQArgs {
   const float* w1; const float* b1; float slope;
   const float* mask; gvp::RngArgs rng; const float* g_out; float* g_x; float* slab;
   const float* agg_in; const uint16_t* pos_in;       // SAVED instantiation: the forward's aggregates [N][CINP] and ReLU patterns
+  // STORE instantiation (deterministic mode, selected by g_edge != NULL): d x[src] of every sorted edge -> g_edge [E][XW],
+  // (1+eps) dh -> g_self [N][XW] (neither when g_self is NULL); quad::src_sum adds them up in a fixed order (g_x unused)
+  float* g_edge; float* g_self;
 };
 
 // dropout factors of channels 16 mt + 4 g .. + 3 of atom n (given mask row of width COUT, or regenerated)
@@ -322,7 +325,7 @@ __device__ __forceinline__ void dw1_band(const f4 (&AT)[Q::MO], const f4 (&BT)[Q
 // (cgvp_gine_fwd_ws.agg / .pos): phase A -- the gather of the source rows (CIN floats per edge), W_e e, ReLU and the segmented
 // sum, 48 % of a tile's cycles in the round-3 stamps -- is replaced by one row load per atom, and the edge phase reads 8 bytes
 // of pattern per edge instead of recomputing the messages.  !SAVED: the fine-grained entry point (no forward workspace).
-template <int CIN, int CHID, int COUT, int NT, int NET, int ED, bool SAVED>
+template <int CIN, int CHID, int COUT, int NT, int NET, int ED, bool SAVED, bool STORE = false>
 __global__ __launch_bounds__((WAVE * GineQ<CIN, CHID, COUT, NT, NET, ED>::WPB)) void gine_quad_bwd_kernel(GineQArgs a) {
   typedef GineQ<CIN, CHID, COUT, NT, NET, ED> Q;
   constexpr int GQ_WPB = Q::WPB, GQ_TPB = Q::TPB;
@@ -555,7 +558,11 @@ __global__ __launch_bounds__((WAVE * GineQ<CIN, CHID, COUT, NT, NET, ED>::WPB)) 
         for (int r = 0; r < 4; ++r) {
           const int c = 16 * mt + 4 * g + r;
           acc_eps = fmaf(dh[mt][r], xi[mt][r], acc_eps);
-          if (a.g_x && valid && c >= NT && c < CIN) atomicAdd(a.g_x + n * XW + (c - NT), eps1 * dh[mt][r]);
+          if constexpr (STORE) {
+            if (a.g_self && valid && c >= NT && c < CIN) a.g_self[n * XW + (c - NT)] = eps1 * dh[mt][r];
+          } else {
+            if (a.g_x && valid && c >= NT && c < CIN) atomicAdd(a.g_x + n * XW + (c - NT), eps1 * dh[mt][r]);
+          }
         }
       }
       WAVE_LDS_SYNC();
@@ -605,8 +612,12 @@ __global__ __launch_bounds__((WAVE * GineQ<CIN, CHID, COUT, NT, NET, ED>::WPB)) 
             const int c = 16 * mt + 4 * g + r;
             dm[mt][r] = ((c_pos[t] >> (4 * mt + r)) & 1u) ? d[r] : 0.f;
             dms[4 * mt + r] = dm[mt][r];
-            if (a.g_x && c >= NT && c < CIN && dm[mt][r] != 0.f)
-              atomicAdd(a.g_x + (int64_t)src * XW + (c - NT), dm[mt][r]);
+            if constexpr (STORE) {        // every channel of every valid position, zeros included
+              if (a.g_self && active && c >= NT && c < CIN) a.g_edge[(int64_t)(c0 + 16 * t + i) * XW + (c - NT)] = dm[mt][r];
+            } else {
+              if (a.g_x && c >= NT && c < CIN && dm[mt][r] != 0.f)
+                atomicAdd(a.g_x + (int64_t)src * XW + (c - NT), dm[mt][r]);
+            }
           }
         }
         f4 AT[MI], BT[1], acc[MI][1];
@@ -806,7 +817,11 @@ int launch(GineQArgs& a, int cap, int* rows, int* row_len, hipStream_t st) {
   int64_t wgs = (tiles + GQ_WPB - 1) / GQ_WPB;
   const int G = (int)(wgs < 1 ? 1 : (wgs > cap ? cap : wgs));
   const size_t lds = (size_t)Q::LDS_FLOATS * sizeof(float);
-  if (a.agg_in && a.pos_in) {
+  if (a.g_edge) {              // deterministic mode: the SAVED path only
+    if (!(a.agg_in && a.pos_in)) return CGVP_ERR_NONDETERMINISTIC;
+    CGVP_SET_DYN_LDS_ONCE((gine_quad_bwd_kernel<CIN, CHID, COUT, NT, NET, ED, true, true>), lds);
+    hipLaunchKernelGGL((gine_quad_bwd_kernel<CIN, CHID, COUT, NT, NET, ED, true, true>), dim3(G), dim3(GQ_TPB), lds, st, a);
+  } else if (a.agg_in && a.pos_in) {
     CGVP_SET_DYN_LDS_ONCE((gine_quad_bwd_kernel<CIN, CHID, COUT, NT, NET, ED, true>), lds);
     hipLaunchKernelGGL((gine_quad_bwd_kernel<CIN, CHID, COUT, NT, NET, ED, true>), dim3(G), dim3(GQ_TPB), lds, st, a);
   } else {
@@ -826,11 +841,12 @@ int gine_bwd(int cin, int chid, int cout, int nt, int net, int ed, const float* 
              const float* eattr, const int64_t* etypes, const int32_t* rowptr, const int32_t* eperm,
              const int32_t* esrc, const int32_t* edst, int64_t N, const cgvp_gine_w* w, float slope,
              const float* mask, gvp::RngArgs rng, const float* g_out, float* g_x, float* slab, int max_workgroups,
-             int* rows, int* row_len, hipStream_t st, const float* agg_in, const uint16_t* pos_in) {
+             int* rows, int* row_len, hipStream_t st, const float* agg_in, const uint16_t* pos_in,
+             float* g_edge, float* g_self) {
   const int cap = max_workgroups <= 0 ? kGineBwdDefaultGrid : (max_workgroups > kGineBwdMaxGrid ? kGineBwdMaxGrid : max_workgroups);
   if (((uintptr_t)agg_in & 15) || ((uintptr_t)pos_in & 1)) return CGVP_ERR_BAD_ARG;
   GineQArgs a{x, ntypes, eattr, etypes, rowptr, eperm, esrc, edst, N, w->eps, w->we, w->be, w->w0, w->b0,
-              w->w1, w->b1, slope, mask, rng, g_out, g_x, slab, agg_in, pos_in};
+              w->w1, w->b1, slope, mask, rng, g_out, g_x, slab, agg_in, pos_in, g_edge, g_self};
   // compiled for the layer shapes of HomoMoleculeGNN_GINE in CASTER-DTA (molecule_gnn.py:240-250)
   if (cin == 52 && chid == 16 && cout == 16 && nt == 11 && net == 5 && ed == 9) return launch<52, 16, 16, 11, 5, 9>(a, cap, rows, row_len, st);
   if (cin == 52 && chid == 16 && cout == 16 && nt == 0 && net == 5 && ed == 9) return launch<52, 16, 16, 0, 5, 9>(a, cap, rows, row_len, st);   // nn.Embedding atom types (11-wide), materialised by the host

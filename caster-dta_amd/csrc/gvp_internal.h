@@ -72,7 +72,28 @@ int node_head_bwd(const float* img_head, const float* imgT_head, const float* h_
                   float* zero_rows, float* slab, int* grid, int bf16, hipStream_t st);
 int conv_bwd(int nt_edge, const float* img, const float* imgT, const float* h, const float* e_emb,
              const int32_t* rowptr, const int32_t* esrc, const int32_t* edst, int64_t N, int64_t E, int mean,
-             const float* g_dh, float* g_src, float* g_dst, float* g_e, float* slab, int* grid, int bf16, hipStream_t st);
+             const float* g_dh, float* g_src, float* g_dst, float* g_e, float* slab, int* grid, int bf16, hipStream_t st,
+             float* g_edge = nullptr, float* slot = nullptr);
+// ---- deterministic mode (CGVP_BWD_DETERMINISTIC): store-then-sum instead of float atomics
+// conv_bwd with g_edge / slot: d h[src] rows -> g_edge [E][28] at their sorted positions, boundary rows -> slot
+// [conv_bwd_max_waves()][28]; g_src is not touched (src_sum fills it).  The waves of the launch are *grid x 8.
+int conv_bwd_max_waves();
+// source-order index of a dst-sorted CSR (gvp_kernels.hip): sptr [N+1], spos [E]: the sorted positions p < rowptr[N] of
+// every source in increasing p.  work: src_index_work_ints(N, E) ints, 16-B aligned, any content.  Five launches.
+int64_t src_index_work_ints(int64_t N, int64_t E);
+int src_index(const int32_t* rowptr, const int32_t* esrc, int64_t N, int64_t E, int32_t* sptr, int32_t* spos,
+              int32_t* work, hipStream_t st);
+// out [N][width] = self (optional) + rows[p] over the source's positions (+ slot rows of conv_bwd's boundary targets)
+int src_sum(int width, const float* rows, const float* self, const int32_t* sptr, const int32_t* spos,
+            const int32_t* rowptr, const float* slot, int64_t waves, int64_t N, float* out, hipStream_t st);
+struct DetBufs { const int32_t* sptr; const int32_t* spos; float* rows; float* slot; };
+int conv_bwd_entry(const cgvp_dims* dims, const cgvp_layout* layout, const float* image, int32_t layer,
+                   const float* h, const float* e_emb, const int32_t* rowptr, const int32_t* esrc,
+                   const int32_t* edst, int64_t N, int64_t E, int32_t aggr_mean, const float* g_dh, float* g_src,
+                   int32_t g_src_zeroed, float* g_dst, float* g_e, float* grad_params, float* workspace,
+                   cgvp_segment* segs, int32_t* nsegs, void* stream, const DetBufs* det);
+// CGVP_DETERMINISTIC=1 in the environment (read once): every backward runs in the deterministic mode
+bool deterministic_env();
 // backward of gvp_edge + LayerNorm from the summed d(edge embedding) of the conv layers (weight gradients only)
 int edge_embed_bwd(int nt_edge, const float* img, const float* imgT, const float* e_s, const float* e_v,
                    const int64_t* etypes, const int32_t* eperm, int64_t E, const float* const* g_e, int n_g,
@@ -89,13 +110,15 @@ int gine_bwd(int cin, int chid, int cout, int nt, int net, int ed, const float* 
              const float* eattr, const int64_t* etypes, const int32_t* rowptr, const int32_t* eperm,
              const int32_t* esrc, const int32_t* edst, int64_t N, const cgvp_gine_w* w, float slope,
              const float* mask, gvp::RngArgs rng, const float* g_out, float* g_x, float* slab, int max_workgroups, int* rows,
-             int* row_len, hipStream_t st, const float* agg_in = nullptr, const uint16_t* pos_in = nullptr);
+             int* row_len, hipStream_t st, const float* agg_in = nullptr, const uint16_t* pos_in = nullptr,
+             float* g_edge = nullptr, float* g_self = nullptr);
 int gine_fwd(int cin, int chid, int cout, int nt, int net, int ed, const float* x, const int64_t* ntypes,
              const float* eattr, const int64_t* etypes, const int32_t* rowptr, const int32_t* eperm,
              const int32_t* esrc, const int32_t* edst, int64_t N, const cgvp_gine_w* w, float slope,
              const float* mask, gvp::RngArgs rng, float* out, float* agg_out, uint16_t* pos_out, hipStream_t st);
 int reduce_slab(const float* slab, int rows, int stride, int col0, int len, float* dst, hipStream_t st);
-int reduce_segments(const cgvp_segment* segs, int nsegs, float* grad_params, hipStream_t st, int overwrite = 0);
+int reduce_segments(const cgvp_segment* segs, int nsegs, float* grad_params, hipStream_t st, int overwrite = 0,
+                    bool store_only = false);
 int bwd_block_sizes(int nt_node, int nt_edge, int* emb, int* conv_edge, int* conv_total, int* node, int* head);
 // gvp_kernels.hip
 void zero_words(void* p, size_t words, hipStream_t s);     // the library's own zero fill (never hipMemsetAsync: see gvp_kernels.hip)

@@ -264,6 +264,44 @@ __global__ void csr_rank_kernel(const int64_t* __restrict__ ei, int64_t N, int64
   esrc[lo + rank] = (int32_t)ei[key];
 }
 
+// ===================================================================== source-order index (deterministic mode)
+// The sorted positions of every SOURCE of a dst-sorted CSR, in increasing position: the read-back order of the per-source
+// sums that replace the d h[src] / d x[src] float atomics (quad::src_sum).  Count / scan / fill as in the CSR build
+// (integer atomics: only the fill order depends on arrival), then each position's rank among its source's positions
+// fixes the order.  The fill counts the counters back down to zero.
+__global__ void src_count_kernel(const int32_t* __restrict__ esrc, const int32_t* __restrict__ rowptr, int64_t N,
+                                 int32_t* __restrict__ cnt) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= rowptr[N]) return;
+  const int32_t s = esrc[p];
+  if (s >= 0 && s < N) atomicAdd(&cnt[s], 1);
+}
+__global__ void src_fill_kernel(const int32_t* __restrict__ esrc, const int32_t* __restrict__ rowptr, int64_t N,
+                                const int32_t* __restrict__ sptr, int32_t* __restrict__ cnt, int32_t* __restrict__ tmp) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int32_t ev = rowptr[N];
+  if (p >= ev) return;
+  const int32_t s = esrc[p];
+  if (s < 0 || s >= N) return;
+  const int32_t pos = sptr[s] + atomicSub(&cnt[s], 1) - 1;
+  if (pos >= 0 && pos < ev) tmp[pos] = (int32_t)p;
+}
+__global__ void src_rank_kernel(const int32_t* __restrict__ esrc, const int32_t* __restrict__ rowptr, int64_t N,
+                                const int32_t* __restrict__ sptr, const int32_t* __restrict__ tmp, int32_t* __restrict__ spos) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int32_t ev = rowptr[N];
+  if (k >= ev) return;
+  const int32_t p = tmp[k];
+  if (p < 0 || p >= ev) return;
+  const int32_t s = esrc[p];
+  if (s < 0 || s >= N) return;
+  const int32_t lo = sptr[s], hi = sptr[s + 1];
+  if (lo < 0 || hi > ev || lo > hi) return;
+  int32_t rank = 0;
+  for (int32_t j = lo; j < hi; ++j) rank += tmp[j] < p ? 1 : 0;
+  spos[lo + rank] = p;
+}
+
 // Batch CSR by CONCATENATION of per-graph CSRs (a dataset's few hundred unique
 // graphs are sorted once; a batch is their blocks shifted by node / edge offsets).  One workgroup
 // per batch slot; `sel[b]` is the slot's graph in the store, whose tables hold LOCAL indices.
@@ -715,9 +753,44 @@ int csr_build(const int64_t* edge_index, int64_t N, int64_t E, int32_t* rowptr, 
                      edst, eperm, esrc, work);
   return launch_status();
 }
+
+bool deterministic_env() {
+  static const bool v = [] { const char* e = getenv("CGVP_DETERMINISTIC"); return e && e[0] == '1'; }();
+  return v;
+}
+
+// work: [counters (N + 1 rounded up to 64) | tmp (E)]
+int64_t src_index_work_ints(int64_t N, int64_t E) { return (N + 1 + 63) / 64 * 64 + (E > 0 ? E : 1); }
+
+int src_index(const int32_t* rowptr, const int32_t* esrc, int64_t N, int64_t E, int32_t* sptr, int32_t* spos,
+              int32_t* work, hipStream_t s) {
+  if (N < 0 || E < 0 || !rowptr || !sptr || !work || (E > 0 && (!esrc || !spos))) return CGVP_ERR_BAD_ARG;
+  if (N >= (int64_t)1 << 31 || E >= (int64_t)1 << 31 || ((uintptr_t)work & 15)) return CGVP_ERR_BAD_ARG;
+  const int64_t counters = (N + 1 + 63) / 64 * 64;
+  int32_t* cnt = work;
+  int32_t* tmp = work + counters;
+  zero_words(cnt, (size_t)counters, s);
+  const int B = 256;
+  const unsigned eb = (unsigned)((E + B - 1) / B);
+  if (E > 0) hipLaunchKernelGGL(src_count_kernel, dim3(eb), dim3(B), 0, s, esrc, rowptr, N, cnt);
+  if (N < SCAN_MULTI_MAX) {
+    hipLaunchKernelGGL(csr_scan_multi_kernel, dim3((unsigned)((N + 1 + SCAN_MULTI_CHUNK - 1) / SCAN_MULTI_CHUNK)),
+                       dim3(SCAN_MULTI_T), 0, s, cnt, (int32_t)N, (int32_t)counters, sptr);
+  } else {
+    const int64_t tile = N < SCAN_LDS ? (N + 3) / 4 * 4 : SCAN_LDS;
+    hipLaunchKernelGGL(csr_scan_kernel, dim3(1), dim3(1024), (size_t)(tile + 1024 + 32) * sizeof(int32_t), s, cnt, N, sptr);
+  }
+  if (E > 0) {
+    hipLaunchKernelGGL(src_fill_kernel, dim3(eb), dim3(B), 0, s, esrc, rowptr, N, sptr, cnt, tmp);
+    hipLaunchKernelGGL(src_rank_kernel, dim3(eb), dim3(B), 0, s, esrc, rowptr, N, sptr, tmp, spos);
+  }
+  return launch_status();
+}
 }  // namespace quad
 
 extern "C" {
+
+int cgvp_deterministic_forced(void) { return quad::deterministic_env() ? 1 : 0; }
 
 int cgvp_csr_collate(const int32_t* st_rowptr, const int32_t* st_eperm, const int32_t* st_esrc,
                      const int32_t* st_edst, const int64_t* st_node_off, const int64_t* st_edge_off,
@@ -989,6 +1062,19 @@ int cgvp_conv_bwd(const cgvp_dims* dims, const cgvp_layout* layout, const float*
                   const int32_t* edst, int64_t N, int64_t E, int32_t aggr_mean, const float* g_dh, float* g_src,
                   int32_t g_src_zeroed, float* g_dst, float* g_e, float* grad_params, float* workspace,
                   cgvp_segment* segs, int32_t* nsegs, void* stream) {
+  if (quad::deterministic_env()) return CGVP_ERR_NONDETERMINISTIC;     // d h[src] by float atomics
+  return quad::conv_bwd_entry(dims, layout, image, layer, h, e_emb, rowptr, esrc, edst, N, E, aggr_mean, g_dh, g_src,
+                              g_src_zeroed, g_dst, g_e, grad_params, workspace, segs, nsegs, stream, nullptr);
+}
+}  // extern "C"
+
+// cgvp_conv_bwd; det != NULL: the deterministic mode (store d h[src] rows, then one per-source sum launch into g_src,
+// which needs no zero fill)
+int quad::conv_bwd_entry(const cgvp_dims* dims, const cgvp_layout* layout, const float* image, int32_t layer,
+                         const float* h, const float* e_emb, const int32_t* rowptr, const int32_t* esrc,
+                         const int32_t* edst, int64_t N, int64_t E, int32_t aggr_mean, const float* g_dh, float* g_src,
+                         int32_t g_src_zeroed, float* g_dst, float* g_e, float* grad_params, float* workspace,
+                         cgvp_segment* segs, int32_t* nsegs, void* stream, const quad::DetBufs* det) {
   if (int rc = check_dims(dims)) return rc;
   if (N < 0 || E < 0 || !layout || !image || !grad_params || !workspace) return CGVP_ERR_BAD_ARG;
   const int nc = num_convs_of(*layout);
@@ -1003,17 +1089,57 @@ int cgvp_conv_bwd(const cgvp_dims* dims, const cgvp_layout* layout, const float*
   int emb, ce, ct, nd, hd, grid = 0;
   if (int rc = quad::bwd_block_sizes(layout->nt_node, layout->nt_edge, &emb, &ce, &ct, &nd, &hd)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (!g_src_zeroed) {
+  if (!g_src_zeroed && !det) {
     zero_words(g_src, (size_t)N * ROW, st);
   }
   if (int rc = quad::conv_bwd(layout->nt_edge, image + o.conv0 + layer * o.layer_stride,
                               image + o.convT0 + layer * o.layerT_stride, h, e_emb, rowptr, esrc, edst, N, E,
-                              aggr_mean ? 1 : 0, g_dh, g_src, g_dst, g_e, workspace, &grid, policy_of(dims), st)) return rc;
+                              aggr_mean ? 1 : 0, g_dh, g_src, g_dst, g_e, workspace, &grid, policy_of(dims), st,
+                              det ? det->rows : nullptr, det ? det->slot : nullptr)) return rc;
+  if (det)
+    if (int rc = quad::src_sum(ROW, det->rows, nullptr, det->sptr, det->spos, rowptr, det->slot, (int64_t)grid * 8, N, g_src, st))
+      return rc;
   cgvp_segment sg[1] = {{workspace, grid, ct, 0, conv_ln0(), layout->conv0 + layer * layout->conv_stride}};
   if (segs && nsegs) { segs[0] = sg[0]; *nsegs = 1; }
-  else quad::reduce_segments(sg, 1, grad_params, st);
+  else quad::reduce_segments(sg, 1, grad_params, st, det ? 1 : 0, det != nullptr);
   return launch_status();
 }
+
+extern "C" {
+
+int64_t cgvp_src_index_work_ints(int64_t num_nodes, int64_t num_edges) {
+  if (num_nodes < 0 || num_edges < 0) return CGVP_ERR_BAD_ARG;
+  return quad::src_index_work_ints(num_nodes, num_edges);
+}
+
+int cgvp_src_index(const int32_t* rowptr, const int32_t* esrc, int64_t num_nodes, int64_t num_edges, int32_t* sptr,
+                   int32_t* spos, int32_t* work, void* stream) {
+  return quad::src_index(rowptr, esrc, num_nodes, num_edges, sptr, spos, work, (hipStream_t)stream);
+}
+
+int64_t cgvp_conv_bwd_det_floats(int64_t num_nodes, int64_t num_edges) {
+  if (num_nodes < 0 || num_edges < 0) return CGVP_ERR_BAD_ARG;
+  return (num_edges > 0 ? num_edges : 1) * ROW + (int64_t)quad::conv_bwd_max_waves() * ROW;
+}
+
+int cgvp_conv_bwd_ex(const cgvp_dims* dims, const cgvp_layout* layout, const float* image, int32_t layer,
+                     const float* h, const float* e_emb, const int32_t* rowptr, const int32_t* esrc,
+                     const int32_t* edst, int64_t N, int64_t E, int32_t aggr_mean, const float* g_dh, float* g_src,
+                     int32_t g_src_zeroed, float* g_dst, float* g_e, float* grad_params, float* workspace,
+                     cgvp_segment* segs, int32_t* nsegs, const int32_t* sptr, const int32_t* spos, float* det_scratch,
+                     int32_t flags, void* stream) {
+  if (!((flags & CGVP_BWD_DETERMINISTIC) || quad::deterministic_env()))
+    return quad::conv_bwd_entry(dims, layout, image, layer, h, e_emb, rowptr, esrc, edst, N, E, aggr_mean, g_dh, g_src,
+                                g_src_zeroed, g_dst, g_e, grad_params, workspace, segs, nsegs, stream, nullptr);
+  if (!sptr || !det_scratch || (E > 0 && !spos) || ((uintptr_t)det_scratch & 15)) return CGVP_ERR_BAD_ARG;
+  const quad::DetBufs db{sptr, spos, det_scratch, det_scratch + (E > 0 ? E : 1) * ROW};
+  return quad::conv_bwd_entry(dims, layout, image, layer, h, e_emb, rowptr, esrc, edst, N, E, aggr_mean, g_dh, g_src,
+                              g_src_zeroed, g_dst, g_e, grad_params, workspace, segs, nsegs, stream, &db);
+}
+
+}  // extern "C"
+
+extern "C" {
 
 int cgvp_edge_embed_bwd(const cgvp_dims* dims, const cgvp_layout* layout, const float* image, const float* e_s,
                         const float* e_v, const int64_t* etypes, const int32_t* eperm, int64_t E,
@@ -1133,6 +1259,7 @@ int cgvp_gine_conv_bwd(const float* x, const int64_t* ntypes, int32_t num_ntypes
                        float* workspace, int32_t max_workgroups, void* stream) {
   if (N < 0 || E < 0 || !w || !grad_layer || !workspace) return CGVP_ERR_BAD_ARG;
   if (int rc = check_rng(rng)) return rc;
+  if (quad::deterministic_env() && g_x) return CGVP_ERR_NONDETERMINISTIC;     // d x by float atomics
   if (N == 0) return 0;
   if (!x || !g_out || !rowptr || (num_ntypes > 0 && !ntypes)) return CGVP_ERR_BAD_ARG;
   if (E > 0 && (!eperm || !esrc || !edst || (edge_dim > 0 && !eattr) || (num_etypes > 0 && !etypes))) return CGVP_ERR_BAD_ARG;

@@ -451,6 +451,9 @@ struct ConvBArgs {
   const float* h; const float* e_emb;
   const int32_t* rowptr; const int32_t* esrc; const int32_t* edst;
   int64_t N; int npw; int mean; const float* g_dh; float* g_src; float* g_dst; float* g_e; float* slab;
+  // deterministic mode (STORE instantiation of conv_bwd2_kernel): d h[src] row of every sorted position -> g_edge [E][28],
+  // the boundary target's partial sum of every wave -> slot [waves][28]; src_sum_kernel adds them up in a fixed order
+  float* g_edge; float* slot;
 };
 
 template <int NTE, typename ST>
@@ -720,7 +723,7 @@ __device__ __forceinline__ void c2_load_rows(const ConvBArgs& a, int32_t pc, int
   }
 }
 
-template <int NTE, typename ST, int TN, int C2_WPB>
+template <int NTE, typename ST, int TN, int C2_WPB, bool STORE = false>
 __global__ __launch_bounds__(WAVE * C2_WPB) __attribute__((amdgpu_waves_per_eu(C2_WPB / 4, C2_WPB / 4))) void conv_bwd2_kernel(ConvBArgs a) {
   WALL_STAMP(2);
   typedef Image<0, NTE> IM;
@@ -963,34 +966,49 @@ __global__ __launch_bounds__(WAVE * C2_WPB) __attribute__((amdgpu_waves_per_eu(C
         }
       }
     STAMP(5);
-    // ---- d h[src]: rows transposed through LDS so that one wave-instruction adds two whole 112-B rows; a self loop's row
-    // joins its target's sum below instead
+    // ---- d h[src].  STORE (deterministic mode): each lane stores its edge's quarter row at the edge's sorted position
+    // (16 B + 12 B; a self loop's row is zero, it joins its target's sum below).  Default: rows transposed through LDS so
+    // that one wave-instruction adds two whole 112-B rows with float atomics; a self loop's row joins its target's sum
     bool self[TN];
+    if constexpr (STORE) {
 #pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      self[j] = active[j] && src[j] == dst[j];
-      float* tr = trow + (j * TILE + i) * ROW;
-      *reinterpret_cast<f4*>(tr + 4 * g) = f4{d_b0[j][0], d_b0[j][1], d_b0[j][2], d_b0[j][3]};
+      for (int j = 0; j < TN; ++j) {
+        self[j] = active[j] && src[j] == dst[j];
+        if (active[j]) {
+          float* row = a.g_edge + (int64_t)(base + j * TILE + i) * ROW;
+          const bool z = self[j];
+          *reinterpret_cast<f4*>(row + 4 * g) = z ? zero : f4{d_b0[j][0], d_b0[j][1], d_b0[j][2], d_b0[j][3]};
 #pragma unroll
-      for (int d = 0; d < 3; ++d) tr[NS + 3 * g + d] = d_bv0[j][d][0];
-      if (g == 0) tsrc[j * TILE + i] = (active[j] && !self[j]) ? src[j] : -1;
-    }
-    __builtin_amdgcn_wave_barrier();
-    {
-      const int half = lane / ROW, col = lane - half * ROW;      // lanes 0..27 -> row 2k, 28..55 -> row 2k+1
-      const int hr = half & 1;                                   // (lanes 56..63 read row 2k too and add nothing)
-      int sr[C2_GS_ROWS / 2];
-      float val[C2_GS_ROWS / 2];
-#pragma unroll
-      for (int k = 0; k < C2_GS_ROWS / 2; ++k) {                 // all the LDS reads first: two round trips, not 32
-        sr[k] = tsrc[2 * k + hr];
-        val[k] = trow[(2 * k + hr) * ROW + (half < 2 ? col : 0)];
+          for (int d = 0; d < 3; ++d) row[NS + 3 * g + d] = z ? 0.f : d_bv0[j][d][0];
+        }
       }
+    } else {
 #pragma unroll
-      for (int k = 0; k < C2_GS_ROWS / 2; ++k)
-        if (half < 2 && sr[k] >= 0) atomicAdd(a.g_src + (int64_t)sr[k] * ROW + col, val[k]);
+      for (int j = 0; j < TN; ++j) {
+        self[j] = active[j] && src[j] == dst[j];
+        float* tr = trow + (j * TILE + i) * ROW;
+        *reinterpret_cast<f4*>(tr + 4 * g) = f4{d_b0[j][0], d_b0[j][1], d_b0[j][2], d_b0[j][3]};
+#pragma unroll
+        for (int d = 0; d < 3; ++d) tr[NS + 3 * g + d] = d_bv0[j][d][0];
+        if (g == 0) tsrc[j * TILE + i] = (active[j] && !self[j]) ? src[j] : -1;
+      }
+      __builtin_amdgcn_wave_barrier();
+      {
+        const int half = lane / ROW, col = lane - half * ROW;      // lanes 0..27 -> row 2k, 28..55 -> row 2k+1
+        const int hr = half & 1;                                   // (lanes 56..63 read row 2k too and add nothing)
+        int sr[C2_GS_ROWS / 2];
+        float val[C2_GS_ROWS / 2];
+#pragma unroll
+        for (int k = 0; k < C2_GS_ROWS / 2; ++k) {                 // all the LDS reads first: two round trips, not 32
+          sr[k] = tsrc[2 * k + hr];
+          val[k] = trow[(2 * k + hr) * ROW + (half < 2 ? col : 0)];
+        }
+#pragma unroll
+        for (int k = 0; k < C2_GS_ROWS / 2; ++k)
+          if (half < 2 && sr[k] >= 0) atomicAdd(a.g_src + (int64_t)sr[k] * ROW + col, val[k]);
+      }
+      __builtin_amdgcn_wave_barrier();
     }
-    __builtin_amdgcn_wave_barrier();
     STAMP(6);
     // ---- d h[dst]: segment sums of the sorted edges (DPP scan + a register carry across tiles), stored where a segment
     // truly ends inside the wave's range
@@ -1017,6 +1035,11 @@ __global__ __launch_bounds__(WAVE * C2_WPB) __attribute__((amdgpu_waves_per_eu(C
       if (active[j] && nxt != dst[j]) {
         if (dst[j] != lead_dst) {
           float* row = a.g_dst + (int64_t)dst[j] * ROW;
+          *reinterpret_cast<f4*>(row + 4 * g) = f4{x[0], x[1], x[2], x[3]};
+#pragma unroll
+          for (int d = 0; d < 3; ++d) row[NS + 3 * g + d] = x[4 + d];
+        } else if constexpr (STORE) {       // at most one lead segment per wave: its own slot
+          float* row = a.slot + wid * ROW;
           *reinterpret_cast<f4*>(row + 4 * g) = f4{x[0], x[1], x[2], x[3]};
 #pragma unroll
           for (int d = 0; d < 3; ++d) row[NS + 3 * g + d] = x[4 + d];
@@ -1289,6 +1312,8 @@ __global__ __launch_bounds__(256) void reduce_rows_kernel(const float* __restric
 }
 
 struct SegTable { cgvp_segment s[CGVP_MAX_SEGS]; };
+// ADD = false: the store-only instantiation of the deterministic mode (no float atomic in its code)
+template <bool ADD = true>
 __global__ __launch_bounds__(RED_COLS * RED_RG) void reduce_segments_kernel(SegTable t, float* __restrict__ grad, int overwrite) {
   __shared__ float part[RED_RG][RED_COLS];
   const cgvp_segment sg = t.s[blockIdx.y];
@@ -1316,13 +1341,14 @@ __global__ __launch_bounds__(RED_COLS * RED_RG) void reduce_segments_kernel(SegT
     float tt = 0.f;
 #pragma unroll
     for (int k = 0; k < RED_RG; ++k) tt += part[k][c];
-    if (overwrite) grad[sg.dst + j] = tt;     // the caller guarantees disjoint destinations that cover what it reads
-    else atomicAdd(grad + sg.dst + j, tt);    // ADD semantics of the per-call reductions
+    if (!ADD || overwrite) grad[sg.dst + j] = tt;     // the caller guarantees disjoint destinations that cover what it reads
+    else atomicAdd(grad + sg.dst + j, tt);            // ADD semantics of the per-call reductions
   }
 }
 
 // the same for segments of a handful of rows (the GINE backward on <= 32 workgroups): one thread per column, small
 // workgroups that fit beside the protein backward's CU-filling kernels
+template <bool ADD = true>
 __global__ __launch_bounds__(256) void reduce_segments_rows_kernel(SegTable t, float* __restrict__ grad, int overwrite) {
   const cgvp_segment sg = t.s[blockIdx.y];
   const int j = blockIdx.x * 256 + threadIdx.x;
@@ -1330,8 +1356,38 @@ __global__ __launch_bounds__(256) void reduce_segments_rows_kernel(SegTable t, f
   const float* col = sg.slab + sg.col0 + j;
   float s = 0.f;
   for (int r = 0; r < sg.rows; ++r) s += col[(size_t)r * sg.stride];
-  if (overwrite) grad[sg.dst + j] = s;
+  if (!ADD || overwrite) grad[sg.dst + j] = s;
   else atomicAdd(grad + sg.dst + j, s);
+}
+
+// ===================================================================== deterministic mode: per-source sums
+// out[n][c] = self[n][c] (optional) + sum of rows[p][c] over the sorted positions p of source n, in increasing p (spos,
+// sptr: quad::src_index) + (slot != NULL, conv_bwd2_kernel STORE) the boundary partial sums of the waves whose edge
+// range starts strictly inside target n's segment, in wave order.  Every row is stored: no zero fill.  One thread per
+// element: a source's rows are read as whole 4*W-byte segments by consecutive threads.
+struct SrcSumArgs {
+  const float* rows; const float* self; const int32_t* sptr; const int32_t* spos;
+  const int32_t* rowptr; const float* slot; int64_t waves; int64_t N; float* out;
+};
+template <int W>
+__global__ __launch_bounds__(256) void src_sum_kernel(SrcSumArgs a) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= a.N * W) return;
+  const int64_t n = t / W;
+  const int c = (int)(t - n * W);
+  float s = a.self ? a.self[t] : 0.f;
+  const int32_t k0 = a.sptr[n], k1 = a.sptr[n + 1];
+#pragma unroll 4
+  for (int32_t k = k0; k < k1; ++k) s += a.rows[(int64_t)a.spos[k] * W + c];
+  if (a.slot) {
+    // the wave ranges of conv_bwd2_kernel<.., TN = 1, ..>: ipw iterations of TILE positions each over rowptr[N] edges
+    const int64_t ev = a.rowptr[a.N];
+    const int64_t iters = (ev + TILE - 1) / TILE, chunk = (iters + a.waves - 1) / a.waves * TILE;
+    const int64_t r0 = a.rowptr[n], r1 = a.rowptr[n + 1];
+    if (chunk > 0)
+      for (int64_t w = r0 / chunk + 1; w * chunk < r1; ++w) s += a.slot[w * W + c];
+  }
+  a.out[t] = s;
 }
 
 // Workgroup cap of the backward kernels.  BW_MAX_GRID (240: slab rows are sized for it) when the launch is
@@ -1374,7 +1430,20 @@ int bwd_block_sizes(int nt_node, int nt_edge, int* emb, int* conv_edge, int* con
   return 0;
 }
 
-int reduce_segments(const cgvp_segment* segs, int nsegs, float* grad_params, hipStream_t st, int overwrite) {
+// store_only: the instantiations without a float atomic in their code (deterministic mode; overwrite semantics, the
+// whole passes' segments have disjoint destinations)
+template <bool ADD>
+void launch_reduce_segments(const SegTable& t, int nsegs, int maxlen, int maxrows, float* grad_params, hipStream_t st,
+                            int overwrite) {
+  if (maxrows <= 32) {
+    hipLaunchKernelGGL(reduce_segments_rows_kernel<ADD>, dim3((maxlen + 255) / 256, nsegs), dim3(256), 0, st, t, grad_params, overwrite);
+    return;
+  }
+  hipLaunchKernelGGL(reduce_segments_kernel<ADD>, dim3((maxlen + RED_COLS - 1) / RED_COLS, nsegs), dim3(RED_COLS * RED_RG), 0,
+                     st, t, grad_params, overwrite);
+}
+
+int reduce_segments(const cgvp_segment* segs, int nsegs, float* grad_params, hipStream_t st, int overwrite, bool store_only) {
   if (nsegs <= 0) return 0;
   SegTable t;
   int maxlen = 0;
@@ -1384,14 +1453,26 @@ int reduce_segments(const cgvp_segment* segs, int nsegs, float* grad_params, hip
     maxlen = segs[i].len > maxlen ? segs[i].len : maxlen;
     maxrows = segs[i].rows > maxrows ? segs[i].rows : maxrows;
   }
-  if (maxrows <= 32) {
-    hipLaunchKernelGGL(reduce_segments_rows_kernel, dim3((maxlen + 255) / 256, nsegs), dim3(256), 0, st, t, grad_params, overwrite);
-    return 0;
-  }
-  hipLaunchKernelGGL(reduce_segments_kernel, dim3((maxlen + RED_COLS - 1) / RED_COLS, nsegs), dim3(RED_COLS * RED_RG), 0,
-                     st, t, grad_params, overwrite);
+  if (store_only) launch_reduce_segments<false>(t, nsegs, maxlen, maxrows, grad_params, st, 1);
+  else launch_reduce_segments<true>(t, nsegs, maxlen, maxrows, grad_params, st, overwrite);
   return 0;
 }
+
+int src_sum(int width, const float* rows, const float* self, const int32_t* sptr, const int32_t* spos,
+            const int32_t* rowptr, const float* slot, int64_t waves, int64_t N, float* out, hipStream_t st) {
+  if (N <= 0) return 0;
+  SrcSumArgs a{rows, self, sptr, spos, rowptr, slot, waves, N, out};
+  const unsigned blocks = (unsigned)((N * width + 255) / 256);
+  switch (width) {
+    case 16: hipLaunchKernelGGL(src_sum_kernel<16>, dim3(blocks), dim3(256), 0, st, a); return 0;
+    case ROW: hipLaunchKernelGGL(src_sum_kernel<ROW>, dim3(blocks), dim3(256), 0, st, a); return 0;
+    case 41: hipLaunchKernelGGL(src_sum_kernel<41>, dim3(blocks), dim3(256), 0, st, a); return 0;
+    case 52: hipLaunchKernelGGL(src_sum_kernel<52>, dim3(blocks), dim3(256), 0, st, a); return 0;
+    default: return CGVP_ERR_UNSUPPORTED_DIMS;
+  }
+}
+
+int conv_bwd_max_waves() { return BW_MAX_GRID * 8; }
 
 int reduce_slab(const float* slab, int rows, int stride, int col0, int len, float* dst, hipStream_t st) {
   if (rows <= 32) {            // a handful of rows: one thread per column, small workgroups that fit beside anything
@@ -1496,7 +1577,7 @@ int conv_bwd_version() {
   return v;
 }
 
-template <int NTE, int TN, int WPB_>
+template <int NTE, int TN, int WPB_, bool STORE = false>
 int conv_bwd2_impl(ConvBArgs& a, int64_t E, int* grid, int bf16, hipStream_t st) {
   typedef C2Shape<TN, WPB_> SH;
   const int64_t iters = (E + TN * TILE - 1) / (TN * TILE);
@@ -1505,7 +1586,7 @@ int conv_bwd2_impl(ConvBArgs& a, int64_t E, int* grid, int bf16, hipStream_t st)
   const int G = (int)(wgs < 1 ? 1 : (wgs > cap ? cap : wgs));
   *grid = G;
   const size_t lds = (size_t)SH::template lds_floats<NTE>() * sizeof(float);
-#define K_(ST) conv_bwd2_kernel<NTE, ST, TN, WPB_>
+#define K_(ST) conv_bwd2_kernel<NTE, ST, TN, WPB_, STORE>
   if (bf16 >= POLICY_GVPDEF) {
     if constexpr (NTE == 0) BWD_LAUNCH_KIND(K_, G, SH::TPB, lds, a);
     else return CGVP_ERR_UNSUPPORTED_DIMS;
@@ -1537,13 +1618,20 @@ int conv_bwd_impl(ConvBArgs& a, int* grid, int bf16, hipStream_t st) {
 
 int conv_bwd(int nt_edge, const float* img, const float* imgT, const float* h, const float* e_emb,
              const int32_t* rowptr, const int32_t* esrc, const int32_t* edst, int64_t N, int64_t E, int mean,
-             const float* g_dh, float* g_src, float* g_dst, float* g_e, float* slab, int* grid, int bf16, hipStream_t st) {
+             const float* g_dh, float* g_src, float* g_dst, float* g_e, float* slab, int* grid, int bf16, hipStream_t st,
+             float* g_edge, float* slot) {
   // targets per wave: two 16-edge tiles' worth (the forward's 32-edge passes), as in quad::conv
   int64_t deg = N > 0 ? (E + N - 1) / N : 1;
   if (deg < 1) deg = 1;
   int npw = (int)((2 * TILE - 2) / deg);
   npw = npw < 1 ? 1 : (npw > WAVE ? WAVE : npw);
-  ConvBArgs a{img, imgT, h, e_emb, rowptr, esrc, edst, N, npw, mean, g_dh, g_src, g_dst, g_e, slab};
+  ConvBArgs a{img, imgT, h, e_emb, rowptr, esrc, edst, N, npw, mean, g_dh, g_src, g_dst, g_e, slab, g_edge, slot};
+  if (g_edge) {         // deterministic mode: the default kernel's STORE instantiation; the A/B kernels have none
+    if (conv_bwd_version() != 3 || !slot) return CGVP_ERR_NONDETERMINISTIC;
+    if (nt_edge == 0) return conv_bwd2_impl<0, 1, 8, true>(a, E, grid, bf16, st);
+    if (nt_edge == 1) return conv_bwd2_impl<1, 1, 8, true>(a, E, grid, bf16, st);
+    return CGVP_ERR_UNSUPPORTED_DIMS;
+  }
   if (conv_bwd_version() == 2) {
     if (nt_edge == 0) return conv_bwd2_impl<0, 2, 4>(a, E, grid, bf16, st);
     if (nt_edge == 1) return conv_bwd2_impl<1, 2, 4>(a, E, grid, bf16, st);

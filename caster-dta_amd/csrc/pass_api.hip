@@ -75,11 +75,23 @@ inline bool has_tables(const cgvp_lba_batch* b) { return b->rowptr != nullptr; }
 inline bool has_tables(const cgvp_gine_batch* b) { return b->rowptr != nullptr; }
 
 // ------------------------------------------------------------------ protein backward workspace
+// deterministic mode: behind the default layout, the source-order index and the stored rows
+struct DetWs { int64_t sptr, spos, work, rows, extra; };
+void take_det(Bump& b, int64_t N, int64_t E, int width, int64_t extra_floats, DetWs* d) {
+  d->sptr = b.take((N + 1) * 4);
+  d->spos = b.take((E > 0 ? E : 1) * 4);
+  d->work = b.take(quad::src_index_work_ints(N, E) * 4);
+  d->rows = b.take((E > 0 ? E : 1) * width * 4);
+  d->extra = b.take(extra_floats * 4);
+}
+inline bool det_mode(int32_t flags) { return (flags & CGVP_BWD_DETERMINISTIC) || quad::deterministic_env(); }
+
 struct LbaBwdWs {
   int64_t slabs, g_e, rows, total;      // per-stage partial weight-gradient slabs | d(edge embedding) per layer | 8 node-row buffers
   int64_t slab_floats, g_e_stride, row_floats;
+  int det; DetWs det_ws;                // rows: d h[src] per sorted edge [E][28]; extra: conv_bwd's boundary slots
 };
-int lba_bwd_layout(const cgvp_dims* dims, const cgvp_layout* layout, int64_t N, int64_t E, LbaBwdWs* w) {
+int lba_bwd_layout(const cgvp_dims* dims, const cgvp_layout* layout, int64_t N, int64_t E, LbaBwdWs* w, bool det = false) {
   const int64_t wsz = cgvp_bwd_workspace_floats(dims, layout);
   if (wsz < 0) return (int)wsz;
   const int nc = num_convs_of(*layout);
@@ -91,6 +103,9 @@ int lba_bwd_layout(const cgvp_dims* dims, const cgvp_layout* layout, int64_t N, 
   w->row_floats = up(N * ROW * 4, 256) / 4;
   w->rows = b.take(8 * w->row_floats * 4);
   w->total = b.off;
+  w->det = 0;
+  if (det) take_det(b, N, E, ROW, ROW * (int64_t)quad::conv_bwd_max_waves(), &w->det_ws);
+  if (det) { w->det = 1; w->total = b.off; }
   return 0;
 }
 
@@ -106,8 +121,8 @@ int check_gine_cfg(const cgvp_gine_cfg* c) {
   if (c->widths[0] <= c->num_ntypes) return CGVP_ERR_BAD_ARG;
   return 0;
 }
-struct GineBwdWs { int64_t slabs, gx, total, slab_floats, gx_floats; };
-void gine_bwd_layout(const cgvp_gine_cfg* c, int64_t N, GineBwdWs* w) {
+struct GineBwdWs { int64_t slabs, gx, total, slab_floats, gx_floats; int det; DetWs det_ws; };   // extra: (1+eps) dh rows
+void gine_bwd_layout(const cgvp_gine_cfg* c, int64_t N, GineBwdWs* w, int64_t E = 0, bool det = false) {
   Bump b;
   w->slab_floats = cgvp_gine_bwd_workspace_floats();
   w->slabs = b.take((int64_t)c->num_layers * w->slab_floats * 4);
@@ -116,6 +131,17 @@ void gine_bwd_layout(const cgvp_gine_cfg* c, int64_t N, GineBwdWs* w) {
   w->gx_floats = up(N * maxw * 4, 256) / 4;           // d h_l for every hidden activation, back to back: ONE zero fill
   w->gx = b.take((int64_t)(c->num_layers - 1) * w->gx_floats * 4);
   w->total = b.off;
+  w->det = 0;
+  if (det) {
+    int maxx = 0;                                        // widest d x row of any layer
+    for (int l = 0; l < c->num_layers; ++l) {
+      const int xw = c->widths[l] - (l == 0 ? c->num_ntypes : 0);
+      maxx = xw > maxx ? xw : maxx;
+    }
+    take_det(b, N, E, maxx, N * maxx, &w->det_ws);
+    w->det = 1;
+    w->total = b.off;
+  }
 }
 
 // ------------------------------------------------------------------ batch staging (cgvp_stage_buffers)
@@ -284,6 +310,15 @@ int cgvp_lba_forward_pass(const cgvp_dims* dims, const cgvp_layout* layout, cons
   return launch_status();
 }
 
+int64_t cgvp_lba_bwd_workspace_bytes_ex(const cgvp_dims* dims, const cgvp_layout* layout, int64_t N, int64_t E,
+                                        int32_t flags) {
+  if (!dims || !layout || N < 0 || E < 0) return CGVP_ERR_BAD_ARG;
+  if (dims->layer_kind != CGVP_LAYER_GATED) return CGVP_ERR_UNSUPPORTED_DIMS;
+  LbaBwdWs w;
+  if (int rc = lba_bwd_layout(dims, layout, N, E, &w, det_mode(flags))) return rc;
+  return w.total;
+}
+
 int64_t cgvp_lba_bwd_workspace_bytes(const cgvp_dims* dims, const cgvp_layout* layout, int64_t N, int64_t E) {
   if (!dims || !layout || N < 0 || E < 0) return CGVP_ERR_BAD_ARG;
   if (dims->layer_kind != CGVP_LAYER_GATED) return CGVP_ERR_UNSUPPORTED_DIMS;
@@ -296,6 +331,16 @@ int cgvp_lba_backward_pass(const cgvp_dims* dims, const cgvp_layout* layout, con
                            int32_t aggr_mean, float dropout_p, const float* masks, const void* fwd_workspace,
                            const float* g_out, void* bwd_workspace, float* grad_params, float* g_x_s, float* g_x_v,
                            float* g_e_s, float* g_e_v, void* stream) {
+  if (quad::deterministic_env()) return CGVP_ERR_NONDETERMINISTIC;     // its workspace has no room for the stored rows
+  return cgvp_lba_backward_pass_ex(dims, layout, batch, aggr_mean, dropout_p, masks, fwd_workspace, g_out, bwd_workspace,
+                                   grad_params, g_x_s, g_x_v, g_e_s, g_e_v, 0, stream);
+}
+
+int cgvp_lba_backward_pass_ex(const cgvp_dims* dims, const cgvp_layout* layout, const cgvp_lba_batch* batch,
+                              int32_t aggr_mean, float dropout_p, const float* masks, const void* fwd_workspace,
+                              const float* g_out, void* bwd_workspace, float* grad_params, float* g_x_s, float* g_x_v,
+                              float* g_e_s, float* g_e_v, int32_t flags, void* stream) {
+  const bool det = det_mode(flags);
   if (!dims || !layout || !batch || !fwd_workspace || !bwd_workspace || !grad_params) return CGVP_ERR_BAD_ARG;
   if (((uintptr_t)fwd_workspace & 255) || ((uintptr_t)bwd_workspace & 255)) return CGVP_ERR_BAD_ARG;
   if ((g_x_s == nullptr) != (g_x_v == nullptr) || (g_e_s == nullptr) != (g_e_v == nullptr)) return CGVP_ERR_BAD_ARG;
@@ -303,7 +348,7 @@ int cgvp_lba_backward_pass(const cgvp_dims* dims, const cgvp_layout* layout, con
   cgvp_lba_fwd_ws ws;
   if (int rc = cgvp_lba_fwd_workspace(dims, layout, N, E, 1, &ws)) return rc;
   LbaBwdWs bw;
-  if (int rc = lba_bwd_layout(dims, layout, N, E, &bw)) return rc;
+  if (int rc = lba_bwd_layout(dims, layout, N, E, &bw, det)) return rc;
   const int nc = num_convs_of(*layout);
   if (nc < 1) return CGVP_ERR_UNSUPPORTED_DIMS;
   hipStream_t st = (hipStream_t)stream;
@@ -338,6 +383,15 @@ int cgvp_lba_backward_pass(const cgvp_dims* dims, const cgvp_layout* layout, con
   auto region = [&]() { return slabs + (int64_t)(stage++) * bw.slab_floats; };
   if (2 * nc + 2 + 1 > CGVP_MAX_SEGS) return CGVP_ERR_UNSUPPORTED_DIMS;
   const int64_t mstride = N * MROW;
+  quad::DetBufs db{};
+  if (det) {             // the source-order index of the batch's CSR, once for every layer
+    const DetWs& d = bw.det_ws;
+    db = quad::DetBufs{at<int32_t>(bwd_workspace, d.sptr), at<int32_t>(bwd_workspace, d.spos),
+                       at<float>(bwd_workspace, d.rows), at<float>(bwd_workspace, d.extra)};
+    if (int rc = quad::src_index(rowptr, esrc, N, E, at<int32_t>(bwd_workspace, d.sptr), at<int32_t>(bwd_workspace, d.spos),
+                                 at<int32_t>(bwd_workspace, d.work), st))
+      return rc;
+  }
   const float *up0 = nullptr, *up1 = nullptr, *up2 = nullptr;
   for (int l = nc - 1; l >= 0; --l) {
     const bool last = l == nc - 1;
@@ -355,8 +409,9 @@ int cgvp_lba_backward_pass(const cgvp_dims* dims, const cgvp_layout* layout, con
     nseg += cnt;
     {
       Timed timed(1, stream);
-      if (int rc = cgvp_conv_bwd(dims, layout, image, l, row(l), e_emb, rowptr, esrc, edst, N, E, aggr_mean, g_dh, g_src, 1,
-                                 g_dst, g_e + (int64_t)l * bw.g_e_stride, grad_params, region(), segs + nseg, &cnt, stream))
+      if (int rc = quad::conv_bwd_entry(dims, layout, image, l, row(l), e_emb, rowptr, esrc, edst, N, E, aggr_mean, g_dh, g_src,
+                                        1, g_dst, g_e + (int64_t)l * bw.g_e_stride, grad_params, region(), segs + nseg, &cnt,
+                                        stream, det ? &db : nullptr))
         return rc;
     }
     nseg += cnt;
@@ -377,7 +432,8 @@ int cgvp_lba_backward_pass(const cgvp_dims* dims, const cgvp_layout* layout, con
   } else {                                               // no edge stage: gvp_edge's gradient block is covered by no segment
     quad::zero_words(grad_params + layout->edge_gvp, (size_t)(layout->conv0 - layout->edge_gvp), st);
   }
-  if (int rc = cgvp_bwd_reduce(segs, nseg, grad_params, 1, stream)) return rc;
+  if (det) quad::reduce_segments(segs, nseg, grad_params, st, 1, true);    // disjoint destinations: stores only
+  else if (int rc = cgvp_bwd_reduce(segs, nseg, grad_params, 1, stream)) return rc;
   return launch_status();
 }
 
@@ -486,16 +542,34 @@ int64_t cgvp_gine_bwd_workspace_bytes(const cgvp_gine_cfg* cfg, int64_t N, int64
   return w.total;
 }
 
+int64_t cgvp_gine_bwd_workspace_bytes_ex(const cgvp_gine_cfg* cfg, int64_t N, int64_t E, int32_t flags) {
+  if (int rc = check_gine_cfg(cfg)) return rc;
+  if (N < 0 || E < 0) return CGVP_ERR_BAD_ARG;
+  GineBwdWs w;
+  gine_bwd_layout(cfg, N, &w, E, det_mode(flags));
+  return w.total;
+}
+
 int cgvp_gine_backward_pass(const cgvp_gine_cfg* cfg, const cgvp_gine_w* w, const cgvp_gine_batch* batch, float dropout_p,
                             const float* const* masks, const void* fwd_workspace, const float* g_out, void* bwd_workspace,
                             float* grad_flat, float* g_x, int32_t max_workgroups, void* stream) {
+  if (quad::deterministic_env()) return CGVP_ERR_NONDETERMINISTIC;     // its workspace has no room for the stored rows
+  return cgvp_gine_backward_pass_ex(cfg, w, batch, dropout_p, masks, fwd_workspace, g_out, bwd_workspace, grad_flat, g_x,
+                                    max_workgroups, 0, stream);
+}
+
+int cgvp_gine_backward_pass_ex(const cgvp_gine_cfg* cfg, const cgvp_gine_w* w, const cgvp_gine_batch* batch, float dropout_p,
+                               const float* const* masks, const void* fwd_workspace, const float* g_out, void* bwd_workspace,
+                               float* grad_flat, float* g_x, int32_t max_workgroups, int32_t flags, void* stream) {
+  const bool det = det_mode(flags);
+  if (det && gine_recompute()) return CGVP_ERR_NONDETERMINISTIC;     // the recomputing kernel has no STORE instantiation
   if (!cfg || !w || !batch || !fwd_workspace || !bwd_workspace || !grad_flat) return CGVP_ERR_BAD_ARG;
   if (((uintptr_t)fwd_workspace & 255) || ((uintptr_t)bwd_workspace & 255)) return CGVP_ERR_BAD_ARG;
   const int64_t N = batch->num_nodes, E = batch->num_edges;
   cgvp_gine_fwd_ws ws;
   if (int rc = cgvp_gine_fwd_workspace(cfg, N, E, 1, &ws)) return rc;
   GineBwdWs bw;
-  gine_bwd_layout(cfg, N, &bw);
+  gine_bwd_layout(cfg, N, &bw, E, det);
   const int L = cfg->num_layers;
   const int ke = cfg->num_etypes + cfg->edge_dim;
   hipStream_t st = (hipStream_t)stream;
@@ -517,9 +591,17 @@ int cgvp_gine_backward_pass(const cgvp_gine_cfg* cfg, const cgvp_gine_w* w, cons
   const int32_t* edst = tables ? batch->edst : at<int32_t>(fwd_workspace, ws.edst);
   float* slabs = at<float>(bwd_workspace, bw.slabs);
   float* gx = at<float>(bwd_workspace, bw.gx);
-  // every d x buffer the layer kernels fill with float atomics, zeroed by ONE launch (the caller's g_x by a second)
-  if (L > 1) quad::zero_words(gx, (size_t)(L - 1) * bw.gx_floats, st);
-  if (g_x) quad::zero_words(g_x, (size_t)N * (cfg->widths[0] - cfg->num_ntypes), st);
+  const DetWs& dw = bw.det_ws;
+  if (det) {
+    // the source-order index; every d x row is then STORED by the per-source sums: no zero fill
+    if (int rc = quad::src_index(rowptr, esrc, N, E, at<int32_t>(bwd_workspace, dw.sptr), at<int32_t>(bwd_workspace, dw.spos),
+                                 at<int32_t>(bwd_workspace, dw.work), st))
+      return rc;
+  } else {
+    // every d x buffer the layer kernels fill with float atomics, zeroed by ONE launch (the caller's g_x by a second)
+    if (L > 1) quad::zero_words(gx, (size_t)(L - 1) * bw.gx_floats, st);
+    if (g_x) quad::zero_words(g_x, (size_t)N * (cfg->widths[0] - cfg->num_ntypes), st);
+  }
   cgvp_segment segs[CGVP_GINE_MAX_LAYERS];
   const float* g = g_out;
   for (int l = L - 1; l >= 0; --l) {
@@ -537,14 +619,22 @@ int cgvp_gine_backward_pass(const cgvp_gine_cfg* cfg, const cgvp_gine_w* w, cons
                                 cfg->num_etypes, cfg->edge_dim, x, first ? batch->ntypes : nullptr, batch->eattr, batch->etypes,
                                 rowptr, eperm, esrc, edst, N, w + l, cfg->act_slope, mask, ra, g, gxl, slab, max_workgroups,
                                 &rows, &row_len, st, gine_recompute() ? nullptr : at<float>(fwd_workspace, ws.agg[l]),
-                                gine_recompute() ? nullptr : at<uint16_t>(fwd_workspace, ws.pos[l])))
+                                gine_recompute() ? nullptr : at<uint16_t>(fwd_workspace, ws.pos[l]),
+                                det ? at<float>(bwd_workspace, dw.rows) : nullptr,          // (the STORE kernel even
+                                (det && gxl) ? at<float>(bwd_workspace, dw.extra) : nullptr))  //  when no d x is wanted)
       return rc;
+    if (det && gxl)
+      if (int rc = quad::src_sum(cfg->widths[l] - (first ? cfg->num_ntypes : 0), at<float>(bwd_workspace, dw.rows),
+                                 at<float>(bwd_workspace, dw.extra), at<int32_t>(bwd_workspace, dw.sptr),
+                                 at<int32_t>(bwd_workspace, dw.spos), rowptr, nullptr, 0, N, gxl, st))
+        return rc;
     segs[l] = cgvp_segment{slab, rows, row_len, 0,
                            gine_layer_floats(cfg->widths[l], cfg->widths[l + 1], cfg->widths[l + 1], ke), loff[l]};
     g = gxl;
   }
   // ONE reduce for all layers; the segments are disjoint and cover grad_flat: stored, no zero fill
-  quad::reduce_segments(segs, L, grad_flat, st, 1);
+  if (det) quad::reduce_segments(segs, L, grad_flat, st, 1, true);
+  else quad::reduce_segments(segs, L, grad_flat, st, 1);
   return launch_status();
 }
 

@@ -53,8 +53,28 @@ void check(int rc, const char* what) {
   if (rc == 0) return;
   if (rc == CGVP_ERR_UNSUPPORTED_DIMS)
     throw NotImplemented(std::string(what) + ": dimensions outside the compiled CASTER-DTA(s,v) configuration");
+  if (rc == CGVP_ERR_NONDETERMINISTIC)
+    throw std::runtime_error(std::string(what) + " does not have a deterministic implementation, but you set "
+                             "'torch.use_deterministic_algorithms(True)' or CGVP_DETERMINISTIC=1");
   if (rc < 0) throw py::value_error(std::string(what) + ": bad argument (code " + std::to_string(rc) + ")");
   throw std::runtime_error(std::string(what) + ": HIP launch failed with hipError_t " + std::to_string(rc));
+}
+
+// the `flags` word of the _ex backward passes: torch's deterministic flag, read when the backward runs (the library ORs in
+// CGVP_DETERMINISTIC=1 itself)
+int32_t bwd_flags() { return at::globalContext().deterministicAlgorithms() ? CGVP_BWD_DETERMINISTIC : 0; }
+// rc of call(flags); a path without a deterministic form returns CGVP_ERR_NONDETERMINISTIC before it launches anything:
+// under use_deterministic_algorithms(True, warn_only=True) it is warned about and run in the default mode
+template <class F>
+int call_bwd(F call, int32_t flags, const char* what) {
+  int rc = call(flags);
+  if (rc == CGVP_ERR_NONDETERMINISTIC && flags && !cgvp_deterministic_forced() &&
+      at::globalContext().deterministicAlgorithmsWarnOnly()) {
+    TORCH_WARN(what, " does not have a deterministic implementation, but you set "
+               "'torch.use_deterministic_algorithms(True, warn_only=True)'");
+    rc = call(0);
+  }
+  return rc;
 }
 
 void* current_stream(const at::Tensor& t) { return (void*)c10::hip::getCurrentHIPStream(t.device().index()).stream(); }
@@ -268,8 +288,9 @@ struct LbaBackward : public Node {
     at::Tensor g_out = ready(grads[0], "grad_output", at::kFloat);
     auto f32 = x_s.options().dtype(at::kFloat).requires_grad(false);
     at::Tensor gparams = at::empty({(int64_t)cfg.layout.total}, f32);
-    const int64_t nbytes = cgvp_lba_bwd_workspace_bytes(&cfg.dims, &cfg.layout, N, E);
-    if (nbytes < 0) check((int)nbytes, "cgvp_lba_bwd_workspace_bytes");
+    const int32_t flags = bwd_flags();
+    const int64_t nbytes = cgvp_lba_bwd_workspace_bytes_ex(&cfg.dims, &cfg.layout, N, E, flags);
+    if (nbytes < 0) check((int)nbytes, "cgvp_lba_bwd_workspace_bytes_ex");
     at::Tensor bws = at::empty({nbytes}, f32.dtype(at::kByte));
     at::Tensor g_x_s, g_x_v;
     if (need_x) {
@@ -282,10 +303,12 @@ struct LbaBackward : public Node {
                      t.rowptr, t.eperm, t.esrc, t.edst};
     {
       Tic tic_c("lba_bwd.c_call");
-      check(cgvp_lba_backward_pass(&cfg.dims, &cfg.layout, &b, cfg.mean, (float)dropout_p, (const float*)ptr(masks), ptr(ws),
-                                   (const float*)ptr(g_out), ptr(bws), (float*)ptr(gparams), (float*)ptr(g_x_s),
-                                   (float*)ptr(g_x_v), nullptr, nullptr, current_stream(x_s)),
-            "cgvp_lba_backward_pass");
+      check(call_bwd([&](int32_t f) {
+              return cgvp_lba_backward_pass_ex(&cfg.dims, &cfg.layout, &b, cfg.mean, (float)dropout_p, (const float*)ptr(masks),
+                                               ptr(ws), (const float*)ptr(g_out), ptr(bws), (float*)ptr(gparams),
+                                               (float*)ptr(g_x_s), (float*)ptr(g_x_v), nullptr, nullptr, f, current_stream(x_s));
+            }, flags, "cgvp_lba_backward_pass_ex"),
+            "cgvp_lba_backward_pass_ex");
     }
     Tic tic_v("lba_bwd.views");
     int64_t off = 0;
@@ -467,8 +490,9 @@ struct GineBackward : public Node {
     int64_t total = 0;
     for (const at::Tensor& p : params) total += p.numel();
     at::Tensor gflat = at::empty({total}, f32);
-    const int64_t nbytes = cgvp_gine_bwd_workspace_bytes(&meta.cfg, N, E);
-    if (nbytes < 0) check((int)nbytes, "cgvp_gine_bwd_workspace_bytes");
+    const int32_t flags = bwd_flags();
+    const int64_t nbytes = cgvp_gine_bwd_workspace_bytes_ex(&meta.cfg, N, E, flags);
+    if (nbytes < 0) check((int)nbytes, "cgvp_gine_bwd_workspace_bytes_ex");
     at::Tensor bws = at::empty({nbytes}, f32.dtype(at::kByte));
     at::Tensor g_x;
     if (need_x) g_x = at::empty({N, (int64_t)(meta.cfg.widths[0] - meta.cfg.num_ntypes)}, f32);
@@ -482,10 +506,12 @@ struct GineBackward : public Node {
     for (const at::Tensor& m : masks) mp.push_back((const float*)ptr(m));
     {
       Tic tic_c("gine_bwd.c_call");
-      check(cgvp_gine_backward_pass(&meta.cfg, w.data(), &b, (float)dropout_p, mp.empty() ? nullptr : mp.data(), ptr(ws),
-                                    (const float*)ptr(g_out), ptr(bws), (float*)ptr(gflat), (float*)ptr(g_x), max_workgroups,
-                                    current_stream(x)),
-            "cgvp_gine_backward_pass");
+      check(call_bwd([&](int32_t f) {
+              return cgvp_gine_backward_pass_ex(&meta.cfg, w.data(), &b, (float)dropout_p, mp.empty() ? nullptr : mp.data(),
+                                                ptr(ws), (const float*)ptr(g_out), ptr(bws), (float*)ptr(gflat), (float*)ptr(g_x),
+                                                max_workgroups, f, current_stream(x));
+            }, flags, "cgvp_gine_backward_pass_ex"),
+            "cgvp_gine_backward_pass_ex");
     }
     if (one_leaf) {
       if (task_should_compute_output(0)) out[0] = gflat;

@@ -15,15 +15,45 @@ import torch  # noqa: F401  (must be imported first: its libamdhip64.so.7 is the
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # CGVP_LIB_PATH: A/B builds of the same ABI (diagnostics); the default is the in-tree library
 LIB_PATH = os.environ.get("CGVP_LIB_PATH") or os.path.join(os.path.dirname(_HERE), "lib", "libcaster_gvp.so")
-ABI_VERSION = 29
+ABI_VERSION = 30
 # sha256 of include/caster_gvp.h with comments, blank space and the CGVP_ABI_VERSION line removed, as
 # `abi_header_digest()` computes it.  tests/test_abi.py fails when the header's declarations change
 # without CGVP_ABI_VERSION, ABI_VERSION and this digest being updated together.
-ABI_HEADER_SHA256 = "362eacc64a468f7a3f91503a8f667d128e3a4dbc6a5b29f605a976517cde6195"
+ABI_HEADER_SHA256 = "ef4411ce177566435316b9ebf051399388ee25c81d11847523b9f4fa13a0c655"
 
 
 class HipLibraryError(RuntimeError):
     pass
+
+
+# ---- deterministic mode of the backward passes (include/caster_gvp.h, CGVP_BWD_DETERMINISTIC)
+BWD_DETERMINISTIC = 1
+ERR_NONDETERMINISTIC = -3
+# CGVP_DETERMINISTIC=1 forces the mode for the whole process (read once, as the library reads it)
+DETERMINISTIC_ENV = os.environ.get("CGVP_DETERMINISTIC", "")[:1] == "1"
+
+
+def deterministic_mode():
+    """True when the backward passes must be bitwise reproducible: torch.use_deterministic_algorithms(True) (read at
+    the time of the call -- backward time, as torch checks its own backward ops) or CGVP_DETERMINISTIC=1."""
+    return DETERMINISTIC_ENV or torch.are_deterministic_algorithms_enabled()
+
+
+def bwd_flags():
+    """The `flags` word of the _ex backward entry points for the current mode."""
+    return BWD_DETERMINISTIC if deterministic_mode() else 0
+
+
+def raise_nondeterministic(what):
+    """torch's rule: an op without a deterministic implementation raises while the mode is on -- or warns, under
+    torch.use_deterministic_algorithms(True, warn_only=True) (the environment switch always raises)."""
+    msg = (f"{what} does not have a deterministic implementation, but you set "
+           "'torch.use_deterministic_algorithms(True)' or CGVP_DETERMINISTIC=1")
+    if not DETERMINISTIC_ENV and torch.is_deterministic_algorithms_warn_only_enabled():
+        import warnings
+        warnings.warn(msg)
+        return
+    raise RuntimeError(msg)
 
 
 class Dims(C.Structure):
@@ -145,12 +175,24 @@ _SIGNATURES = {
                                         _P, _P, _I32, _I32, _P, _P]),
     "cgvp_lba_forward_plan": (C.c_int, [_I64, _I64, _I32, _I32, _I32, C.POINTER(_I32)]),
     "cgvp_lba_bwd_workspace_bytes": (C.c_int64, [C.POINTER(Dims), C.POINTER(Layout), _I64, _I64]),
+    "cgvp_lba_bwd_workspace_bytes_ex": (C.c_int64, [C.POINTER(Dims), C.POINTER(Layout), _I64, _I64, _I32]),
+    "cgvp_lba_backward_pass_ex": (C.c_int, [C.POINTER(Dims), C.POINTER(Layout), C.POINTER(LbaBatch), _I32, C.c_float, _P,
+                                            _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P]),
+    "cgvp_deterministic_forced": (C.c_int, []),
+    "cgvp_src_index_work_ints": (C.c_int64, [_I64, _I64]),
+    "cgvp_src_index": (C.c_int, [_P, _P, _I64, _I64, _P, _P, _P, _P]),
+    "cgvp_conv_bwd_det_floats": (C.c_int64, [_I64, _I64]),
+    "cgvp_conv_bwd_ex": (C.c_int, [C.POINTER(Dims), C.POINTER(Layout), _P, _I32, _P, _P, _P, _P, _P, _I64, _I64, _I32, _P,
+                                   _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P]),
     "cgvp_lba_backward_pass": (C.c_int, [C.POINTER(Dims), C.POINTER(Layout), C.POINTER(LbaBatch), _I32, C.c_float, _P, _P,
                                          _P, _P, _P, _P, _P, _P, _P, _P]),
     "cgvp_gine_fwd_workspace": (C.c_int, [C.POINTER(GineCfg), _I64, _I64, _I32, C.POINTER(GineFwdWs)]),
     "cgvp_gine_forward_pass": (C.c_int, [C.POINTER(GineCfg), C.POINTER(GineW), C.POINTER(GineBatch), C.c_float, _P, _P, _P,
                                          _P, _I32, _I32, _P, _P]),
     "cgvp_gine_bwd_workspace_bytes": (C.c_int64, [C.POINTER(GineCfg), _I64, _I64]),
+    "cgvp_gine_bwd_workspace_bytes_ex": (C.c_int64, [C.POINTER(GineCfg), _I64, _I64, _I32]),
+    "cgvp_gine_backward_pass_ex": (C.c_int, [C.POINTER(GineCfg), C.POINTER(GineW), C.POINTER(GineBatch), C.c_float, _P, _P,
+                                             _P, _P, _P, _P, _I32, _I32, _P]),
     "cgvp_gine_backward_pass": (C.c_int, [C.POINTER(GineCfg), C.POINTER(GineW), C.POINTER(GineBatch), C.c_float, _P, _P,
                                           _P, _P, _P, _P, _I32, _P]),
     "cgvp_linear_wgrad_workspace_floats": (C.c_int64, [_I64, _I32, _I32]),
@@ -240,9 +282,22 @@ def bridge():
     return _bridge
 
 
+def call_bwd(fn, flags, what):
+    """rc of fn(flags), a backward entry point that takes the `flags` word.  A path without a deterministic form returns
+    ERR_NONDETERMINISTIC before it launches anything: under warn_only it is warned about and run in the default mode."""
+    rc = fn(flags)
+    if rc == ERR_NONDETERMINISTIC and flags and not DETERMINISTIC_ENV and torch.is_deterministic_algorithms_warn_only_enabled():
+        raise_nondeterministic(what)
+        rc = fn(0)
+    return rc
+
+
 def check(rc, what):
     if rc == 0:
         return
+    if rc == ERR_NONDETERMINISTIC:
+        raise RuntimeError(f"{what} does not have a deterministic implementation, but you set "
+                           "'torch.use_deterministic_algorithms(True)' or CGVP_DETERMINISTIC=1")
     if rc == -2:
         raise NotImplementedError(
             f"{what}: dimensions outside the compiled CASTER-DTA(s,v) configuration "

@@ -306,9 +306,10 @@ def lba_backward(g_out, x_s, x_v, ntypes, e_s, e_v, etypes, edge_index, csr, ws,
     g_out = _f32(g_out.float(), "grad_output")               # every gradient buffer is fp32, whatever the storage type
     f32 = dict(dtype=torch.float32, device=dev)
     gparams = torch.empty(layout.total, **f32)               # every element is STORED by the pass's final reduce
-    nbytes = int(L.cgvp_lba_bwd_workspace_bytes(C.byref(dims), C.byref(layout), N, E))
+    flags = _lib.bwd_flags()                                 # the deterministic mode is read at backward time
+    nbytes = int(L.cgvp_lba_bwd_workspace_bytes_ex(C.byref(dims), C.byref(layout), N, E, flags))
     if nbytes < 0:
-        _lib.check(nbytes, "cgvp_lba_bwd_workspace_bytes")
+        _lib.check(nbytes, "cgvp_lba_bwd_workspace_bytes_ex")
     bws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     g_x_s = torch.empty(N, dims.node_in_s, **f32) if need_x else None
     g_x_v = torch.empty(N, dims.node_in_v, 3, **f32) if need_x else None
@@ -321,10 +322,11 @@ def lba_backward(g_out, x_s, x_v, ntypes, e_s, e_v, etypes, edge_index, csr, ws,
     if ws.data_ptr() % 256:
         ws = ws.clone()
     with torch.cuda.device(dev):
-        rc = L.cgvp_lba_backward_pass(C.byref(dims), C.byref(layout), C.byref(batch), 1 if mean else 0, float(dropout_p),
-                                      _ptr(masks), _ptr(ws), _ptr(g_out), _ptr(bws), _ptr(gparams), _ptr(g_x_s),
-                                      _ptr(g_x_v), _ptr(g_e_s if E > 0 else None), _ptr(g_e_v if E > 0 else None), _stream())
-    _lib.check(rc, "cgvp_lba_backward_pass")
+        rc = _lib.call_bwd(lambda f: L.cgvp_lba_backward_pass_ex(
+            C.byref(dims), C.byref(layout), C.byref(batch), 1 if mean else 0, float(dropout_p), _ptr(masks), _ptr(ws),
+            _ptr(g_out), _ptr(bws), _ptr(gparams), _ptr(g_x_s), _ptr(g_x_v), _ptr(g_e_s if E > 0 else None),
+            _ptr(g_e_v if E > 0 else None), f, _stream()), flags, "cgvp_lba_backward_pass_ex")
+    _lib.check(rc, "cgvp_lba_backward_pass_ex")
     none = lambda: torch.empty(0, **f32)                     # (outputs of a custom op must not alias each other)
     return (gparams, g_x_s if need_x else none(), g_x_v if need_x else none(), g_e_s if need_e else none(),
             g_e_v if need_e else none())
@@ -597,18 +599,20 @@ def gine_backward(g_out, params, x, ntypes, eattr, etypes, edge_index, csr, ws, 
     et = _i64(etypes, "etypes") if num_etypes > 0 else None
     g = _f32(g_out, "grad_output")
     gflat = torch.empty(sum(p.numel() for p in params), **f32)        # every element is STORED by the pass's reduce
-    nbytes = int(L.cgvp_gine_bwd_workspace_bytes(C.byref(cfg), N, E))
+    flags = _lib.bwd_flags()                                 # the deterministic mode is read at backward time
+    nbytes = int(L.cgvp_gine_bwd_workspace_bytes_ex(C.byref(cfg), N, E, flags))
     if nbytes < 0:
-        _lib.check(nbytes, "cgvp_gine_bwd_workspace_bytes")
+        _lib.check(nbytes, "cgvp_gine_bwd_workspace_bytes_ex")
     bws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     g_x = torch.empty(N, widths[0] - num_ntypes, **f32) if need_x else None
     batch = _gine_batch(x, nt, eattr, et, edge_index, csr, N, E)
     if ws.data_ptr() % 256:
         ws = ws.clone()
     with torch.cuda.device(dev):
-        rc = L.cgvp_gine_backward_pass(C.byref(cfg), warr, C.byref(batch), float(dropout_p), _mask_ptrs(masks, nl), _ptr(ws),
-                                       _ptr(g), _ptr(bws), _ptr(gflat), _ptr(g_x), int(bwd_workgroups), _stream())
-    _lib.check(rc, "cgvp_gine_backward_pass")
+        rc = _lib.call_bwd(lambda f: L.cgvp_gine_backward_pass_ex(
+            C.byref(cfg), warr, C.byref(batch), float(dropout_p), _mask_ptrs(masks, nl), _ptr(ws), _ptr(g), _ptr(bws),
+            _ptr(gflat), _ptr(g_x), int(bwd_workgroups), f, _stream()), flags, "cgvp_gine_backward_pass_ex")
+    _lib.check(rc, "cgvp_gine_backward_pass_ex")
     return gflat, (g_x if need_x else torch.empty(0, **f32))
 
 

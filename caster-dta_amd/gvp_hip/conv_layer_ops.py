@@ -236,14 +236,31 @@ class _ConvFn(torch.autograd.Function):
         g_src, g_dst, g_e = torch.empty(N, ROW, **f32), torch.empty(N, ROW, **f32), torch.zeros(E + 1, EROW, **f32)
         gparams = torch.zeros(layout.total, **f32)
         segs, cnt = (_lib.Segment * 2)(), C.c_int32(0)
+        flags = _lib.bwd_flags()                 # the deterministic mode is read at backward time
         with torch.cuda.device(h.device):
             st = _stream()
             ws = _workspace(dims, layout, h.device)
-            _lib.check(L.cgvp_conv_bwd(C.byref(dims), C.byref(layout), _ptr(image), 0, _ptr(h), _ptr(e_rows),
-                                       _ptr(rowptr), _ptr(esrc), _ptr(edst), N, E, 1 if ctx.mean else 0, _ptr(g_dh),
-                                       _ptr(g_src), 0, _ptr(g_dst), _ptr(g_e), _ptr(gparams), _ptr(ws), segs,
-                                       C.byref(cnt), st), "cgvp_conv_bwd")
-            _reduce(L, segs, cnt.value, gparams, st)
+            if flags:
+                # store-then-sum: the source-order index of this call's CSR, the stored d h[src] rows and the wave slots;
+                # the layer's weight gradients are STORED into its block of gparams (no float atomics anywhere)
+                i32 = dict(dtype=torch.int32, device=h.device)
+                sptr, spos = torch.empty(N + 1, **i32), torch.empty(max(E, 1), **i32)
+                work = torch.empty(int(L.cgvp_src_index_work_ints(N, E)), **i32)
+                _lib.check(L.cgvp_src_index(_ptr(rowptr), _ptr(esrc), N, E, _ptr(sptr), _ptr(spos), _ptr(work), st),
+                           "cgvp_src_index")
+                scratch = torch.empty(int(L.cgvp_conv_bwd_det_floats(N, E)), **f32)
+                rc = _lib.call_bwd(lambda f: L.cgvp_conv_bwd_ex(
+                    C.byref(dims), C.byref(layout), _ptr(image), 0, _ptr(h), _ptr(e_rows), _ptr(rowptr), _ptr(esrc),
+                    _ptr(edst), N, E, 1 if ctx.mean else 0, _ptr(g_dh), _ptr(g_src), 0, _ptr(g_dst), _ptr(g_e),
+                    _ptr(gparams), _ptr(ws), None, None, _ptr(sptr), _ptr(spos), _ptr(scratch), f, st), flags,
+                    "cgvp_conv_bwd_ex")
+                _lib.check(rc, "cgvp_conv_bwd_ex")
+            else:
+                _lib.check(L.cgvp_conv_bwd(C.byref(dims), C.byref(layout), _ptr(image), 0, _ptr(h), _ptr(e_rows),
+                                           _ptr(rowptr), _ptr(esrc), _ptr(edst), N, E, 1 if ctx.mean else 0, _ptr(g_dh),
+                                           _ptr(g_src), 0, _ptr(g_dst), _ptr(g_e), _ptr(gparams), _ptr(ws), segs,
+                                           C.byref(cnt), st), "cgvp_conv_bwd")
+                _reduce(L, segs, cnt.value, gparams, st)
         return gparams, g_src + g_dst, g_e, None, None, None, None, None, None
 
 

@@ -27,6 +27,13 @@ import torch
 from . import _lib, ops
 
 
+def mode_key(key, sdt):
+    """Dictionary key of a bucket: its sizes, the storage dtype and the deterministic mode of the backward passes
+    (torch.use_deterministic_algorithms / CGVP_DETERMINISTIC), so a graph captured in one mode is never replayed in the
+    other."""
+    return (key, sdt, _lib.deterministic_mode())
+
+
 def bucket_size(n):
     """n rounded up to a multiple of 2^(floor(log2 n) - 3): at most 12.5 % larger, 8 buckets per octave."""
     n = int(n)
@@ -118,7 +125,7 @@ class GraphedEncoderStep:
         Na, Ea = mdata["x"].shape[0], mdata["edge_index"].shape[1]
         key = (self.quantum(N), self.quantum(E), self.quantum(Na), self.quantum(Ea))
         sdt = torch.bfloat16 if pdata["x"][0].dtype == torch.bfloat16 else torch.float32
-        b = self.buckets.get((key, sdt))
+        b = self.buckets.get(mode_key(key, sdt))
         if b is not None and b.graph is not None:
             # steady state: stage + replay on the caller's stream (a graph replays on whatever stream it is launched on;
             # no cross-stream dependency, which costs ~10 us of idle device per hop)
@@ -132,7 +139,7 @@ class GraphedEncoderStep:
         self.stream.wait_stream(caller)
         with torch.cuda.stream(self.stream), torch.set_grad_enabled(self.train):
             if b is None:
-                b = self.buckets[(key, sdt)] = _Bucket(self, key, pdata, mdata, sdt)
+                b = self.buckets[mode_key(key, sdt)] = _Bucket(self, key, pdata, mdata, sdt)
             keep = self._stage(b, pdata, mdata, g_res, g_atm)
             old = ops.CSR_CACHE_ENABLED
             ops.CSR_CACHE_ENABLED = False                    # the captured step rebuilds its CSR tables from the staged edge_index
@@ -291,7 +298,7 @@ class GraphedTrainStep:
         B = int(pdata["ptr"].numel()) - 1
         key = (self.quantum(N + 1), self.quantum(E), self.quantum(Na + 1), self.quantum(Ea), B)
         sdt = torch.bfloat16 if pdata["x"][0].dtype == torch.bfloat16 else torch.float32
-        b = self.buckets.get((key, sdt))
+        b = self.buckets.get(mode_key(key, sdt))
         if b is not None and b.graph is not None:
             keep = self._stage(b, pdata, mdata, target)
             b.graph.replay()
@@ -306,7 +313,7 @@ class GraphedTrainStep:
         with torch.cuda.stream(self.stream), torch.enable_grad():
             _check_no_foreign_graph(self.params)
             if b is None:
-                b = self.buckets[(key, sdt)] = _TrainBucket(self, key, pdata, mdata, target, sdt)
+                b = self.buckets[mode_key(key, sdt)] = _TrainBucket(self, key, pdata, mdata, target, sdt)
             keep = self._stage(b, pdata, mdata, target)
             old = ops.CSR_CACHE_ENABLED
             ops.CSR_CACHE_ENABLED = False

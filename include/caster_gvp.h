@@ -27,9 +27,12 @@
 extern "C" {
 #endif
 
-#define CGVP_ABI_VERSION 29
+#define CGVP_ABI_VERSION 30
 #define CGVP_ERR_BAD_ARG (-1)
 #define CGVP_ERR_UNSUPPORTED_DIMS (-2)
+/* the call would add floats in arrival order while the deterministic mode is on (CGVP_BWD_DETERMINISTIC in `flags`, or
+ * CGVP_DETERMINISTIC=1 in the environment): that path has no deterministic implementation */
+#define CGVP_ERR_NONDETERMINISTIC (-3)
 
 /* PARAMETER ARENA.  All weights of VectorProteinGNN_LBAModel live in ONE
  * contiguous fp32 buffer, in the reference's state_dict order with the
@@ -504,6 +507,39 @@ int cgvp_lba_backward_pass(const cgvp_dims* dims, const cgvp_layout* layout, con
                            int32_t aggr_mean, float dropout_p, const float* masks, const void* fwd_workspace,
                            const float* g_out, void* bwd_workspace, float* grad_params, float* g_x_s, float* g_x_v,
                            float* g_e_s, float* g_e_v, void* stream);
+/* DETERMINISTIC MODE of the backward passes (flags & CGVP_BWD_DETERMINISTIC, or CGVP_DETERMINISTIC=1 in the environment,
+ * read once per process): no float atomics -- every d h[src] / d x[src] row is STORED at its sorted edge position and a
+ * per-source kernel sums them in a fixed order (increasing sorted position), so two calls on the same inputs give bitwise
+ * equal results.  Same math as the default mode, sums in another order.  The _ex workspace queries size for the mode
+ * (the default size plus the stored rows and the source-order index); with flags = 0 and the environment switch off they
+ * return what the plain queries return and the _ex passes run exactly the default launches.  The plain entry points,
+ * cgvp_conv_bwd (fine-grained) and cgvp_gine_conv_bwd return CGVP_ERR_NONDETERMINISTIC while the environment switch is on. */
+#define CGVP_BWD_DETERMINISTIC 1
+int64_t cgvp_lba_bwd_workspace_bytes_ex(const cgvp_dims* dims, const cgvp_layout* layout, int64_t num_nodes,
+                                        int64_t num_edges, int32_t flags);
+int cgvp_lba_backward_pass_ex(const cgvp_dims* dims, const cgvp_layout* layout, const cgvp_lba_batch* batch,
+                              int32_t aggr_mean, float dropout_p, const float* masks, const void* fwd_workspace,
+                              const float* g_out, void* bwd_workspace, float* grad_params, float* g_x_s, float* g_x_v,
+                              float* g_e_s, float* g_e_v, int32_t flags, void* stream);
+/* 1 when CGVP_DETERMINISTIC=1 forces the mode for this process, else 0 (host only) */
+int cgvp_deterministic_forced(void);
+/* The source-order index of a dst-sorted CSR (rowptr / esrc as cgvp_csr_from_coo builds them): sptr [N+1] and spos [E]
+ * list the sorted positions p < rowptr[N] of every source node in increasing p -- the order in which the deterministic
+ * mode sums the stored d h[src] rows.  work: cgvp_src_index_work_ints(N, E) int32, 16-B aligned, any content. */
+int64_t cgvp_src_index_work_ints(int64_t num_nodes, int64_t num_edges);
+int cgvp_src_index(const int32_t* rowptr, const int32_t* esrc, int64_t num_nodes, int64_t num_edges, int32_t* sptr,
+                   int32_t* spos, int32_t* work, void* stream);
+/* cgvp_conv_bwd with `flags` (see above).  In the deterministic mode it reads the index of cgvp_src_index (sptr, spos)
+ * and uses det_scratch (cgvp_conv_bwd_det_floats(N, E) floats, 16-B aligned) for the stored rows; g_src is then STORED
+ * (every row: no zero fill), and with segs == NULL the weight gradients OVERWRITE the layer's block of grad_params.
+ * With flags = 0 and the environment switch off it is cgvp_conv_bwd (sptr, spos, det_scratch unused). */
+int64_t cgvp_conv_bwd_det_floats(int64_t num_nodes, int64_t num_edges);
+int cgvp_conv_bwd_ex(const cgvp_dims* dims, const cgvp_layout* layout, const float* image, int32_t layer,
+                     const float* h, const float* e_emb, const int32_t* rowptr, const int32_t* esrc,
+                     const int32_t* edst, int64_t num_nodes, int64_t num_edges, int32_t aggr_mean, const float* g_dh,
+                     float* g_src, int32_t g_src_zeroed, float* g_dst, float* g_e, float* grad_params, float* workspace,
+                     cgvp_segment* segs, int32_t* nsegs, const int32_t* sptr, const int32_t* spos, float* det_scratch,
+                     int32_t flags, void* stream);
 
 #define CGVP_GINE_MAX_LAYERS 8
 typedef struct {
@@ -547,6 +583,13 @@ int64_t cgvp_gine_bwd_workspace_bytes(const cgvp_gine_cfg* cfg, int64_t num_node
 int cgvp_gine_backward_pass(const cgvp_gine_cfg* cfg, const cgvp_gine_w* w, const cgvp_gine_batch* batch,
                             float dropout_p, const float* const* masks, const void* fwd_workspace, const float* g_out,
                             void* bwd_workspace, float* grad_flat, float* g_x, int32_t max_workgroups, void* stream);
+/* the deterministic mode of the two above (see cgvp_lba_backward_pass_ex); CGVP_GINE_RECOMPUTE=1 has no deterministic
+ * implementation (CGVP_ERR_NONDETERMINISTIC) */
+int64_t cgvp_gine_bwd_workspace_bytes_ex(const cgvp_gine_cfg* cfg, int64_t num_nodes, int64_t num_edges, int32_t flags);
+int cgvp_gine_backward_pass_ex(const cgvp_gine_cfg* cfg, const cgvp_gine_w* w, const cgvp_gine_batch* batch,
+                               float dropout_p, const float* const* masks, const void* fwd_workspace, const float* g_out,
+                               void* bwd_workspace, float* grad_flat, float* g_x, int32_t max_workgroups, int32_t flags,
+                               void* stream);
 
 /* ------------------------------------------------------------ ROW-WISE LINEAR LAYERS OF THE HEAD: weight gradients
  * The joint head applies nn.Linear layers to every residue / atom row (joint_gnn.py:188-198, :376-389).  Their weight and
