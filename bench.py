@@ -9,7 +9,8 @@ scaling) and the step ends with the two collectives data-parallel training of th
 all-gather of the per-pair embeddings [pairs, 512] fp32 (joint_gnn.py:272) and ONE flat all-reduce of the encoder
 weight gradients.  Timing: barrier + synchronize on both sides, MAX over ranks.
 
-Prints ONE JSON line (DESIGN.md "Measurement" defines `roofline` and `cpu_baseline`).
+Prints ONE JSON line.  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line; the
+legs beside the headline (roofline, CPU baseline, collated CSR, epochs: DESIGN.md "Measurement") run with --full only.
 """
 import argparse
 import hashlib
@@ -55,11 +56,15 @@ MATRIX_PIPE_CYCLES_PER_US = 1024 * 2400.0       # 1,024 SIMDs at 2.4 GHz
 DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: total size of the written arrays
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the legs that take runs of their own (rank 0): the roofline of the "
+                         "dominant conv kernel, the collated-CSR step, the epoch legs (--epoch) and the CPU baseline; off by "
+                         "default, when those fields of the line are null")
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS))
     ap.add_argument("--config", type=int, default=2, choices=[2, 3, 4, 5],
                     help="BASELINE.json configuration (1-based as DESIGN.md counts them): 2 = Davis batch 64 (default, "
@@ -78,7 +83,7 @@ def parse():
     ap.add_argument("--collate-csr", action="store_true",
                     help="per step, assemble the batch CSR from per-graph CSRs sorted once (SURVEY 8 f-2 wire format) "
                          "instead of sorting the batch's COO edge list; not the default")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--drug-stream", default="side", choices=["side", "main"],
                     help="diagnostic: 'main' runs the drug encoder on the protein stream (no overlap)")
     ap.add_argument("--compile", action="store_true",
@@ -108,12 +113,13 @@ def parse():
     ap.add_argument("--dtype", default=None, choices=["f32", "bf16"],
                     help="activation storage of the protein encoder (bf16 = BASELINE config 5: bf16 storage / fp32 "
                          "accumulate; gradients and weights stay fp32; the drug encoder stays fp32 storage)")
-    ap.add_argument("--epoch", default="both", choices=["off", "nominal", "real", "both"],
-                    help="second leg (N = 1, --scope encoders, davis_b64 only): ONE EPOCH the way train_model.py:548-587 drives "
+    ap.add_argument("--epoch", default=None, choices=["off", "nominal", "real", "both"],
+                    help="--full leg (N = 1, --scope encoders, davis_b64 only): ONE EPOCH the way train_model.py:548-587 drives "
                          "the model -- 329 DIFFERENT batches of 64 pairs drawn from 442 unique proteins x 68 unique drugs (the "
                          "Davis table sizes), a new edge_index every step, eager (no HIP graph); 'nominal' = 300-residue "
                          "proteins, 'real' = lengths drawn from the Davis sequence-length table (mean 789), 'both' (default) = the "
-                         "nominal epoch in config.epoch and the real-length one (eager + bucketed legs) in config.epoch_real")
+                         "nominal epoch in config.epoch and the real-length one (eager + bucketed legs) in config.epoch_real; "
+                         "'off' also skips the collated-CSR leg")
     ap.add_argument("--epoch-steps", type=int, default=329, help="batches in the epoch leg (Davis: 21,039 train pairs / 64)")
     ap.add_argument("--cpu-runs", type=int, default=20, help="timed CPU-baseline runs per thread count (median)")
     ap.add_argument("--cpu-pairs", type=int, default=0, help="pairs in the CPU sample (0 = choose for ~10-30 s)")
@@ -121,9 +127,12 @@ def parse():
                     help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy in "
                          "float32: the encoder outputs and every gradient the step returns (or the affinities, --scope joint "
                          "forward); a seeded row sample once the arrays pass %d MB" % (DUMP_LIMIT_BYTES >> 20))
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be >= 1")
+    if args.epoch not in (None, "off") and not args.full:
+        ap.error(f"--epoch {args.epoch} is a leg of --full")
+    args.epoch = args.epoch or ("both" if args.full else "off")
     wl, dt = {2: ("davis_b64", "f32"), 3: ("kiba_b32", "f32"), 4: ("long_graph_x64", "f32"), 5: ("bindingdb_b32_44", "bf16")}[args.config]
     args.workload = args.workload or wl
     args.dtype = args.dtype or dt
@@ -523,7 +532,7 @@ def main():
 
         # ---- roofline leg: per-launch duration of the dominant conv kernel, HIP events on its launch stream
         roof = None
-        if rank == 0:
+        if rank == 0 and args.full:
             # the library's opt-in diagnostics bracket every conv-layer launch of the whole-pass entry points with HIP
             # events on the launch stream (cgvp_debug_kernel_timing; eager steps, outside the timed region above)
             import ctypes
@@ -583,7 +592,7 @@ def main():
     # CSR tables sorted once at "dataset load", ONE collate launch per encoder per step (the headline above keeps the
     # build in the step: the reference hands over a new COO list every step)
     collated = None
-    if rank == 0 and world == 1 and graph is not None and args.scope == "encoders" and args.only is None \
+    if args.full and rank == 0 and world == 1 and graph is not None and args.scope == "encoders" and args.only is None \
             and not args.collate_csr and not args.cache_csr and not collectives and args.epoch != "off":
         collate = (store_of(pb, pdata), store_of(mb, mdata))
         old_cache, ops.CSR_CACHE_ENABLED = ops.CSR_CACHE_ENABLED, True
@@ -615,7 +624,7 @@ def main():
             ops.CSR_CACHE_ENABLED = old_cache
 
     epoch = epoch_real = None
-    if rank == 0 and world == 1 and args.epoch != "off" and args.scope == "encoders" and args.workload == "davis_b64" \
+    if args.full and rank == 0 and world == 1 and args.epoch != "off" and args.scope == "encoders" and args.workload == "davis_b64" \
             and args.only is None and not collectives:
         if args.epoch in ("real", "both"):                       # first: its fused-parameters leg (nominal only) cannot be undone
             epoch_real = epoch_leg(args, model, dev, train, prot_params, drug_params, variant="real", light=args.epoch == "both")
@@ -625,7 +634,7 @@ def main():
             epoch, epoch_real = epoch_real, None
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:      # a reported baseline of the N = 1 line only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:      # a reported baseline of the N = 1 line only
         cpu = cpu_baseline(args, wl, state, pb, mb, train)
 
     if rank == 0:
@@ -655,7 +664,7 @@ def main():
                        "baseline_config": args.config, "rccl_ranks": (dist.get_world_size() if (dist is not None and not rehearsal) else 0),
                        "timed_region": ("replays of ONE captured step on one batch (CSR build, dropout draw and weight-image build "
                                         "inside every replay)" if graph is not None else "eager steps on one batch"),
-                       "collated_csr": collated, "epoch": epoch, "epoch_real": epoch_real},
+                       "full": bool(args.full), "collated_csr": collated, "epoch": epoch, "epoch_real": epoch_real},
             "roofline": roof, "cpu_baseline": cpu,
         }
         print(json.dumps(line))

@@ -13,8 +13,8 @@ from conftest import REPO, rel_err
 ARGS = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--epoch", "off", "--no-cpu-baseline"]
 
 
-def _bench(out_dir):
-    res = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), *ARGS, "--dump-outputs", str(out_dir)],
+def _bench(out_dir, args=ARGS):
+    res = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), *args, "--dump-outputs", str(out_dir)],
                          capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -40,3 +40,14 @@ def test_bench_dump_outputs_repeat_run_to_run(tmp_path):
         # measured); an unseeded dropout draw moves every array by O(1)
         tol = 5e-2 if k.startswith("grad.protein_gnn.gnn_model.gvp_edge.") else 1e-5
         assert rel_err(b[k], a[k]) < tol, k
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_reports_the_headline_alone(tmp_path):
+    """Without --full the run stops after the timed steps and their outputs: every side leg's field is null."""
+    line, a = _bench(tmp_path / "plain", ["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert line["steps"] == 3 and line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "graph-pairs/sec"
+    assert line["config"]["full"] is False
+    assert line["roofline"] is None and line["cpu_baseline"] is None
+    assert all(line["config"][k] is None for k in ("collated_csr", "epoch", "epoch_real"))
+    assert {"residues", "atoms"} <= set(a)

@@ -69,6 +69,21 @@ def test_bench_rejects_a_world_size_that_contradicts_gpus():
     assert out.returncode != 0 and "WORLD_SIZE=4" in out.stderr
 
 
+def test_bench_side_legs_only_with_full():
+    """A plain run times the headline alone: the epoch legs are off unless --full asks for them, and asking for one
+    without --full is an error rather than a silently empty field."""
+    import pytest
+    bench, _ = _bench_module()
+    plain = bench.parse(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert not plain.full and plain.epoch == "off"
+    assert bench.parse(["--epoch", "off", "--no-cpu-baseline"]).epoch == "off"
+    full = bench.parse(["--full"])
+    assert full.full and full.epoch == "both"
+    assert bench.parse(["--full", "--epoch", "real"]).epoch == "real"
+    with pytest.raises(SystemExit):
+        bench.parse(["--epoch", "nominal"])
+
+
 def test_bench_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
     """--dump-outputs: every array lands as <name>.npy; past the size limit each multi-row array keeps the same seeded
     row sample on every call, with the row indices beside it, and the files stay within the limit."""

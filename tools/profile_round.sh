@@ -9,7 +9,7 @@ case " $* " in *" bf16 "*) TAG=${WL}_bf16;; esac
 OUT=gpurun_out/prof_${RND}_${TAG}
 mkdir -p "$OUT" profiles/$RND
 export TMPDIR=/tmp
-python bench.py --workload $WL "$@" > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --workload $WL "$@" > $OUT/bench.json 2> $OUT/bench.err
 tail -1 $OUT/bench.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o run -- python3 bench.py --workload $WL --no-cpu-baseline --epoch off --steps 100 "$@" > $OUT/stats.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o run -- python3 bench.py --workload $WL --no-cpu-baseline --epoch off --no-graph --steps 10 --warmup 2 "$@" > $OUT/fetch.log 2>&1
