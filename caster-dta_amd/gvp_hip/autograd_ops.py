@@ -69,21 +69,26 @@ _RNG_STATE = {}
 _LAST_WS = {}
 
 
-def rng_state(kind, device):
-    key = (kind, device.index)
+def _persistent_rng(registry, key, device):
+    """registry[key] = [generator seed it was drawn from, persistent int64[2] {seed, offset}]: created on first use,
+    re-seeded in place (never replaced) once the generator's seed has changed; returns the state tensor."""
     gen_seed = torch.cuda.default_generators[device.index].initial_seed()
-    hit = _RNG_STATE.get(key)
+    hit = registry.get(key)
     if hit is None or hit[0] != gen_seed:
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("the dropout generator state must exist before HIP-graph capture: run one training "
                                "step eagerly first (any warm-up does)")
+        seed = draw_seed(device)
         if hit is None:
-            hit = [gen_seed, draw_seed(device)]
-            _RNG_STATE[key] = hit
+            registry[key] = hit = [gen_seed, seed]
         else:
-            hit[1].copy_(draw_seed(device))
+            hit[1].copy_(seed)
             hit[0] = gen_seed
     return hit[1]
+
+
+def rng_state(kind, device):
+    return _persistent_rng(_RNG_STATE, (kind, device.index), device)
 
 
 def last_seed(kind):

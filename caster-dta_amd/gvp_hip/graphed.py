@@ -19,6 +19,7 @@ step, all-reduce) before the next `run` of the same bucket.  Opt-in: the nn.Modu
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -44,9 +45,10 @@ def bucket_size(n):
 
 
 class _Bucket:
-    def __init__(self, owner, key, pdata, mdata, sdt):
-        N, E, Na, Ea = key
-        dev = owner.device
+    """Static inputs of one shape bucket -- the protein and drug dicts padded to (N, E) and (Na, Ea) rows, edge_index
+    filled with -1 -- and its captured step (`graph`, outputs `out`, replay count `steps`)."""
+
+    def __init__(self, dev, N, E, Na, Ea, pdata, mdata, sdt):
         z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=dev)
         ni = pdata["x"][0].shape[1], pdata["x"][1].shape[1], pdata["eattr"][0].shape[1], pdata["eattr"][1].shape[1]
         self.p = dict(x=(z(N, ni[0], dt=sdt), z(N, ni[1], 3, dt=sdt)), edge_index=torch.full((2, E), -1, dtype=torch.int64, device=dev),
@@ -54,51 +56,19 @@ class _Bucket:
                       eattr=(z(E, ni[2], dt=sdt), z(E, ni[3], 3, dt=sdt)))
         self.m = dict(x=z(Na, mdata["x"].shape[1]), edge_index=torch.full((2, Ea), -1, dtype=torch.int64, device=dev),
                       ntypes=z(Na, dt=torch.int64), etypes=z(Ea, dt=torch.int64), eattr=z(Ea, mdata["eattr"].shape[1]))
-        self.g_res, self.g_atm = z(N, owner.out_res, dt=sdt), z(Na, owner.out_atm)
-        self.graph, self.out = None, None
-        self.steps = 0
+        self.graph, self.out, self.steps = None, None, 0
 
 
-class GraphedEncoderStep:
-    """step = forward of both encoders + backward with every weight gradient, protein chain on the launch stream, drug
-    chain on a side stream (what bench.py times).  `run(pdata, mdata, g_res, g_atm)` -> (residues [N, 64],
-    atoms [Na, 64], protein grads, drug grads) -- views of static tensors of the batch's bucket."""
+class _BucketedGraphs:
+    """Capture-or-replay core of both steps.  A subclass supplies `_new_bucket`, `_pairs` (its staging pairs after the ten
+    feature tensors), `_step` and `_capture_mode` (the context of a bucket's creation, warm-up and capture)."""
 
-    def __init__(self, protein_gnn, molecule_gnn, train=True, quantum=bucket_size):
-        self.prot, self.mol = protein_gnn, molecule_gnn
-        self.pp = [p for p in protein_gnn.parameters() if p.numel()]
-        self.mp = [p for p in molecule_gnn.parameters() if p.numel()]
-        self.device = self.pp[0].device
-        self.out_res = protein_gnn.out_channels[0] if isinstance(protein_gnn.out_channels, (tuple, list)) else protein_gnn.out_channels
-        self.out_atm = molecule_gnn.out_channels
-        self.train, self.quantum = train, quantum
-        self.buckets = {}
-        self.stream = torch.cuda.Stream(device=self.device)          # capture + replay stream (its CSR counters persist)
-        self.side = torch.cuda.Stream(device=self.device)
-        self.pool = None
-
-    def _step(self, b):
-        main_s = torch.cuda.current_stream()
-        self.side.wait_stream(main_s)
-        res = self.prot(**b.p)
-        with torch.cuda.stream(self.side):
-            atm = self.mol(**b.m)
-        if not self.train:
-            main_s.wait_stream(self.side)
-            return res, atm, (), ()
-        gp = torch.autograd.grad([res], self.pp, [b.g_res])
-        with torch.cuda.stream(self.side):
-            gd = torch.autograd.grad([atm], self.mp, [b.g_atm])
-        main_s.wait_stream(self.side)
-        return res, atm, gp, gd
-
-    def _stage(self, b, pdata, mdata, g_res, g_atm):
+    def _stage(self, b, pdata, mdata, extra):
+        """ONE launch copies the batch into b's static buffers; returns the sources that must outlive the copy."""
         pairs = [(b.p["x"][0], pdata["x"][0]), (b.p["x"][1], pdata["x"][1]), (b.p["ntypes"], pdata["ntypes"]),
                  (b.p["etypes"], pdata["etypes"]), (b.p["eattr"][0], pdata["eattr"][0]), (b.p["eattr"][1], pdata["eattr"][1]),
                  (b.m["x"], mdata["x"]), (b.m["ntypes"], mdata["ntypes"]), (b.m["etypes"], mdata["etypes"]),
-                 (b.m["eattr"], mdata["eattr"])]
-        if self.train:
-            pairs += [(b.g_res, g_res), (b.g_atm, g_atm)]
+                 (b.m["eattr"], mdata["eattr"])] + extra
         items = (_lib.StageItem * _lib.MAX_STAGE)()
         keep, k = [], 0
         for dst, src in pairs:
@@ -120,27 +90,24 @@ class GraphedEncoderStep:
                        "cgvp_stage_buffers")
         return keep
 
-    def run(self, pdata, mdata, g_res=None, g_atm=None):
-        N, E = pdata["x"][0].shape[0], pdata["edge_index"].shape[1]
-        Na, Ea = mdata["x"].shape[0], mdata["edge_index"].shape[1]
-        key = (self.quantum(N), self.quantum(E), self.quantum(Na), self.quantum(Ea))
+    def _replay(self, key, pdata, mdata, *extra):
+        """Stage the batch and replay its bucket's graph (captured at the first visit); returns the bucket."""
         sdt = torch.bfloat16 if pdata["x"][0].dtype == torch.bfloat16 else torch.float32
         b = self.buckets.get(mode_key(key, sdt))
         if b is not None and b.graph is not None:
             # steady state: stage + replay on the caller's stream (a graph replays on whatever stream it is launched on;
             # no cross-stream dependency, which costs ~10 us of idle device per hop)
-            keep = self._stage(b, pdata, mdata, g_res, g_atm)
+            keep = self._stage(b, pdata, mdata, self._pairs(b, pdata, mdata, *extra))
             b.graph.replay()
             b.steps += 1
             del keep                                         # same stream: the allocator's stream ordering covers the reuse
-            res, atm, gp, gd = b.out
-            return res[:N], atm[:Na], gp, gd
+            return b
         caller = torch.cuda.current_stream()
         self.stream.wait_stream(caller)
-        with torch.cuda.stream(self.stream), torch.set_grad_enabled(self.train):
+        with torch.cuda.stream(self.stream), self._capture_mode():
             if b is None:
-                b = self.buckets[mode_key(key, sdt)] = _Bucket(self, key, pdata, mdata, sdt)
-            keep = self._stage(b, pdata, mdata, g_res, g_atm)
+                b = self.buckets[mode_key(key, sdt)] = self._new_bucket(key, sdt, pdata, mdata, *extra)
+            keep = self._stage(b, pdata, mdata, self._pairs(b, pdata, mdata, *extra))
             old = ops.CSR_CACHE_ENABLED
             ops.CSR_CACHE_ENABLED = False                    # the captured step rebuilds its CSR tables from the staged edge_index
             try:
@@ -160,7 +127,60 @@ class GraphedEncoderStep:
         caller.wait_stream(self.stream)
         for t in keep:
             t.record_stream(self.stream)
-        res, atm, gp, gd = b.out
+        return b
+
+
+class GraphedEncoderStep(_BucketedGraphs):
+    """step = forward of both encoders + backward with every weight gradient, protein chain on the launch stream, drug
+    chain on a side stream (what bench.py times).  `run(pdata, mdata, g_res, g_atm)` -> (residues [N, 64],
+    atoms [Na, 64], protein grads, drug grads) -- views of static tensors of the batch's bucket."""
+
+    def __init__(self, protein_gnn, molecule_gnn, train=True, quantum=bucket_size):
+        self.prot, self.mol = protein_gnn, molecule_gnn
+        self.pp = [p for p in protein_gnn.parameters() if p.numel()]
+        self.mp = [p for p in molecule_gnn.parameters() if p.numel()]
+        self.device = self.pp[0].device
+        self.out_res = protein_gnn.out_channels[0] if isinstance(protein_gnn.out_channels, (tuple, list)) else protein_gnn.out_channels
+        self.out_atm = molecule_gnn.out_channels
+        self.train, self.quantum = train, quantum
+        self.buckets = {}
+        self.stream = torch.cuda.Stream(device=self.device)          # capture + replay stream (its CSR counters persist)
+        self.side = torch.cuda.Stream(device=self.device)
+        self.pool = None
+
+    def _new_bucket(self, key, sdt, pdata, mdata, g_res, g_atm):
+        N, E, Na, Ea = key
+        b = _Bucket(self.device, N, E, Na, Ea, pdata, mdata, sdt)
+        b.g_res = torch.zeros(N, self.out_res, dtype=sdt, device=self.device)
+        b.g_atm = torch.zeros(Na, self.out_atm, dtype=torch.float32, device=self.device)
+        return b
+
+    def _pairs(self, b, pdata, mdata, g_res, g_atm):
+        return [(b.g_res, g_res), (b.g_atm, g_atm)] if self.train else []
+
+    def _capture_mode(self):
+        return torch.set_grad_enabled(self.train)
+
+    def _step(self, b):
+        main_s = torch.cuda.current_stream()
+        self.side.wait_stream(main_s)
+        res = self.prot(**b.p)
+        with torch.cuda.stream(self.side):
+            atm = self.mol(**b.m)
+        if not self.train:
+            main_s.wait_stream(self.side)
+            return res, atm, (), ()
+        gp = torch.autograd.grad([res], self.pp, [b.g_res])
+        with torch.cuda.stream(self.side):
+            gd = torch.autograd.grad([atm], self.mp, [b.g_atm])
+        main_s.wait_stream(self.side)
+        return res, atm, gp, gd
+
+    def run(self, pdata, mdata, g_res=None, g_atm=None):
+        N, E = pdata["x"][0].shape[0], pdata["edge_index"].shape[1]
+        Na, Ea = mdata["x"].shape[0], mdata["edge_index"].shape[1]
+        key = (self.quantum(N), self.quantum(E), self.quantum(Na), self.quantum(Ea))
+        res, atm, gp, gd = self._replay(key, pdata, mdata, g_res, g_atm).out
         return res[:N], atm[:Na], gp, gd
 
 
@@ -180,28 +200,7 @@ def _check_no_foreign_graph(params):
             "Drop those tensors first (`del loss, pred`), or run the eager step after the captured one.")
 
 
-class _TrainBucket:
-    def __init__(self, owner, key, pdata, mdata, target, sdt):
-        N, E, Na, Ea, B = key
-        dev = owner.device
-        z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=dev)
-        ni = pdata["x"][0].shape[1], pdata["x"][1].shape[1], pdata["eattr"][0].shape[1], pdata["eattr"][1].shape[1]
-        # B real pairs + ONE padding pair that owns every padded residue / atom (never empty: the sizes are rounded up from
-        # n + 1), so that the head's per-pair pooling and attention see B + 1 well-formed pairs and the loss reads the first B
-        pptr = torch.full((B + 2,), N, dtype=torch.int64, device=dev)
-        mptr = torch.full((B + 2,), Na, dtype=torch.int64, device=dev)
-        self.p = dict(x=(z(N, ni[0], dt=sdt), z(N, ni[1], 3, dt=sdt)), edge_index=torch.full((2, E), -1, dtype=torch.int64, device=dev),
-                      ntypes=z(N, dt=torch.int64), etypes=z(E, dt=torch.int64),
-                      eattr=(z(E, ni[2], dt=sdt), z(E, ni[3], 3, dt=sdt)), ptr=pptr)
-        self.m = dict(x=z(Na, mdata["x"].shape[1]), edge_index=torch.full((2, Ea), -1, dtype=torch.int64, device=dev),
-                      ntypes=z(Na, dt=torch.int64), etypes=z(Ea, dt=torch.int64), eattr=z(Ea, mdata["eattr"].shape[1]), ptr=mptr)
-        self.target = torch.zeros((B,) + tuple(target.shape[1:]), dtype=target.dtype, device=dev)
-        self.rows_p = torch.arange(N, device=dev)
-        self.rows_m = torch.arange(Na, device=dev)
-        self.graph, self.out, self.steps = None, None, 0
-
-
-class GraphedTrainStep:
+class GraphedTrainStep(_BucketedGraphs):
     """The WHOLE JointGNN training step -- forward of both encoders and the head, loss, backward with all 764k gradients --
     replayed from shape-bucketed HIP graphs, for the loop of train_model.py:548-587 that feeds a different batch every step:
 
@@ -226,11 +225,34 @@ class GraphedTrainStep:
         self.params = [p for p in model.parameters() if p.numel() and p.requires_grad]
         self.device = self.params[0].device
         self.buckets = {}
-        self.stream = None                      # capture + replay stream, created at the first capture
+        self.stream = torch.cuda.Stream(device=self.device)          # capture + replay stream
         self.pool = None
 
-    def _step(self, b, B):
-        import contextlib
+    def _new_bucket(self, key, sdt, pdata, mdata, target):
+        N, E, Na, Ea, B = key
+        dev = self.device
+        b = _Bucket(dev, N, E, Na, Ea, pdata, mdata, sdt)
+        # B real pairs + ONE padding pair that owns every padded residue / atom (never empty: the sizes are rounded up from
+        # n + 1), so that the head's per-pair pooling and attention see B + 1 well-formed pairs and the loss reads the first B
+        b.p["ptr"] = torch.full((B + 2,), N, dtype=torch.int64, device=dev)
+        b.m["ptr"] = torch.full((B + 2,), Na, dtype=torch.int64, device=dev)
+        b.target = torch.zeros((B,) + tuple(target.shape[1:]), dtype=target.dtype, device=dev)
+        b.rows_p, b.rows_m = torch.arange(N, device=dev), torch.arange(Na, device=dev)
+        return b
+
+    def _pairs(self, b, pdata, mdata, target):
+        return [(b.target, target), (b.p["ptr"][:-1], pdata["ptr"]), (b.m["ptr"][:-1], mdata["ptr"])]   # (the last offset stays the padded size)
+
+    @contextlib.contextmanager
+    def _capture_mode(self):
+        was_training = self.model.training
+        with torch.enable_grad():
+            _check_no_foreign_graph(self.params)     # before the bucket is created or staged
+            yield
+        self.model.train(was_training)
+
+    def _step(self, b):
+        B = len(b.target)                               # real pairs
         ctx = torch.autocast("cuda", dtype=self.autocast) if self.autocast is not None else contextlib.nullcontext()
         # pair index of every row from the staged offsets (no host sync): rows behind the last real one -> the padding pair B
         pd = dict(b.p, batch=self._pair_of_rows(b.p["ptr"], b.rows_p))
@@ -256,33 +278,6 @@ class GraphedTrainStep:
             return torch.searchsorted(ptr[1:].contiguous(), rows, right=True)
         return (rows.unsqueeze(1) >= ptr[1:].unsqueeze(0)).sum(dim=1)
 
-    def _stage(self, b, pdata, mdata, target):
-        pairs = [(b.p["x"][0], pdata["x"][0]), (b.p["x"][1], pdata["x"][1]), (b.p["ntypes"], pdata["ntypes"]),
-                 (b.p["etypes"], pdata["etypes"]), (b.p["eattr"][0], pdata["eattr"][0]), (b.p["eattr"][1], pdata["eattr"][1]),
-                 (b.m["x"], mdata["x"]), (b.m["ntypes"], mdata["ntypes"]), (b.m["etypes"], mdata["etypes"]),
-                 (b.m["eattr"], mdata["eattr"]), (b.target, target),
-                 (b.p["ptr"][:-1], pdata["ptr"]), (b.m["ptr"][:-1], mdata["ptr"])]      # (the last offset stays the padded size)
-        items = (_lib.StageItem * _lib.MAX_STAGE)()
-        keep, k = [], 0
-        for dst, src in pairs:
-            if src.dtype != dst.dtype or not src.is_contiguous():
-                src = src.to(dst.dtype).contiguous()
-                keep.append(src)
-            items[k] = _lib.StageItem(dst.data_ptr(), src.data_ptr() if src.numel() else 0, src.numel() * src.element_size(),
-                                      dst.numel() * dst.element_size(), 0)
-            k += 1
-        for dst, src in ((b.p["edge_index"], pdata["edge_index"]), (b.m["edge_index"], mdata["edge_index"])):
-            src = src.contiguous()
-            keep.append(src)
-            E, Ecap = src.shape[1], dst.shape[1]
-            for row in range(2):
-                items[k] = _lib.StageItem(dst[row].data_ptr(), src[row].data_ptr() if E else 0, E * 8, Ecap * 8, 0xFFFFFFFF)
-                k += 1
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().cgvp_stage_buffers(items, k, C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                       "cgvp_stage_buffers")
-        return keep
-
     def _publish(self, b):
         loss, pred, grads = b.out
         for p, g in zip(self.params, grads):
@@ -297,42 +292,4 @@ class GraphedTrainStep:
         Na, Ea = mdata["x"].shape[0], mdata["edge_index"].shape[1]
         B = int(pdata["ptr"].numel()) - 1
         key = (self.quantum(N + 1), self.quantum(E), self.quantum(Na + 1), self.quantum(Ea), B)
-        sdt = torch.bfloat16 if pdata["x"][0].dtype == torch.bfloat16 else torch.float32
-        b = self.buckets.get(mode_key(key, sdt))
-        if b is not None and b.graph is not None:
-            keep = self._stage(b, pdata, mdata, target)
-            b.graph.replay()
-            b.steps += 1
-            del keep
-            return self._publish(b)
-        caller = torch.cuda.current_stream()
-        if self.stream is None:
-            self.stream = torch.cuda.Stream(device=self.device)
-        self.stream.wait_stream(caller)
-        was_training = self.model.training
-        with torch.cuda.stream(self.stream), torch.enable_grad():
-            _check_no_foreign_graph(self.params)
-            if b is None:
-                b = self.buckets[mode_key(key, sdt)] = _TrainBucket(self, key, pdata, mdata, target, sdt)
-            keep = self._stage(b, pdata, mdata, target)
-            old = ops.CSR_CACHE_ENABLED
-            ops.CSR_CACHE_ENABLED = False
-            try:
-                for _ in range(2):
-                    self._step(b, B)
-                torch.cuda.current_stream().synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, stream=self.stream, pool=self.pool):
-                    b.out = self._step(b, B)
-                if self.pool is None:
-                    self.pool = g.pool()
-                b.graph = g
-            finally:
-                ops.CSR_CACHE_ENABLED = old
-            b.graph.replay()
-            b.steps += 1
-        caller.wait_stream(self.stream)
-        for t in keep:
-            t.record_stream(self.stream)
-        self.model.train(was_training)
-        return self._publish(b)
+        return self._publish(self._replay(key, pdata, mdata, target))

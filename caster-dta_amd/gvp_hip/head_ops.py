@@ -185,19 +185,7 @@ def _head_rng_state(device):
     """Persistent device-side generator state of the head's fused dropout sites (never replaced: captured graphs keep
     its address; re-seeded in place after torch.manual_seed)."""
     from . import autograd_ops
-    gen_seed = torch.cuda.default_generators[device.index].initial_seed()
-    hit = _HEAD_RNG.get(device.index)
-    if hit is None or hit[0] != gen_seed:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("the dropout generator state must exist before HIP-graph capture: run one training step "
-                               "eagerly first (any warm-up does)")
-        seed = autograd_ops.draw_seed(device)
-        if hit is None:
-            _HEAD_RNG[device.index] = hit = [gen_seed, seed]
-        else:
-            hit[1].copy_(seed)
-            hit[0] = gen_seed
-    return hit[1]
+    return autograd_ops._persistent_rng(_HEAD_RNG, device.index, device)
 
 
 @torch.library.custom_op("caster_gvp::rng_next", mutates_args=("state",), device_types="cuda")

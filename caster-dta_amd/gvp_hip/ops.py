@@ -272,24 +272,6 @@ def fuse_layer(num_nodes, num_edges):
     16-lane tile): a win for radius graphs (3-4 edges per residue), a loss for dense kNN graphs where a
     wave owns one or two targets and would run a nearly empty node tile."""
     return FUSE_LAYER and num_edges <= 4 * num_nodes
-# bench.py's roofline leg: when this is a list, every conv launch appends a
-# (start, end) pair of timing events recorded on the launch stream.
-KERNEL_EVENTS = None
-
-
-class _timed:
-    def __init__(self, name):
-        self.name = name
-
-    def __enter__(self):
-        if KERNEL_EVENTS is not None:
-            self.ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            self.ev[0].record()
-
-    def __exit__(self, *exc):
-        if KERNEL_EVENTS is not None:
-            self.ev[1].record()
-            KERNEL_EVENTS.append((self.name,) + self.ev)
 
 
 def csr_memo(edge_index, num_nodes):
@@ -307,10 +289,9 @@ def cached_csr(edge_index, num_nodes, counted=None):
     backward pass share one build.  The memo dies with the tensor and is ignored
     after any in-place write (`_version` bump); a different tensor object -- every
     freshly collated training batch -- is always rebuilt."""
-    if CSR_CACHE_ENABLED:
-        memo = getattr(edge_index, "_cgvp_csr", None)
-        if memo is not None and memo[0] == edge_index._version and memo[1].num_nodes == num_nodes:
-            return memo[1]
+    csr = csr_memo(edge_index, num_nodes)
+    if csr is not None:
+        return csr
     csr = build_csr(edge_index, num_nodes, counted)
     if CSR_CACHE_ENABLED:
         try:
@@ -318,26 +299,6 @@ def cached_csr(edge_index, num_nodes, counted=None):
         except (AttributeError, RuntimeError):
             pass
     return csr
-
-
-def csr_for_forward(edge_index, num_nodes, counted=None):
-    """`cached_csr`, plus a forward -> backward hand-off that does not depend on CSR_CACHE_ENABLED: the tables
-    of the latest forward over this tensor object are left on it for the backward of the same step (autograd
-    hands the saved `edge_index` back as the same Python object in eager mode)."""
-    csr = cached_csr(edge_index, num_nodes, counted)
-    try:
-        edge_index._cgvp_csr_step = (edge_index._version, csr)
-    except (AttributeError, RuntimeError):
-        pass
-    return csr
-
-
-def csr_for_backward(edge_index, num_nodes):
-    memo = getattr(edge_index, "_cgvp_csr_step", None)
-    if memo is not None and memo[0] == edge_index._version and memo[1].num_nodes == num_nodes \
-            and memo[1].num_edges == int(edge_index.shape[1]) and memo[1].rowptr.device == edge_index.device:
-        return memo[1]
-    return cached_csr(edge_index, num_nodes)      # e.g. under torch.compile: a different tensor object
 
 
 def edge_features(ca_xyz, seq_index, edge_index):
@@ -418,22 +379,20 @@ def lba_encoder_forward(params, layout, dims, num_convs, x_s, x_v, ntypes, e_s, 
             if fuse_layer(N, E) and VARIANT == "mfma" and not return_stages:
                 # one launch per GVPConvLayer: conv + node update (+ output head); no dh buffer in inference
                 last = layer == num_convs - 1
-                with _timed("conv_fwd"):
-                    _lib.check(L.cgvp_conv_layer_fwd(d, lay, I, layer, _ptr(h), _ptr(e_s), _ptr(e_v), _ptr(et),
-                                                     _ptr(csr.rowptr), _ptr(csr.eperm), _ptr(csr.esrc),
-                                                     _ptr(csr.edst), N, E, 1 if aggr_mean else 0, C.c_void_p(0),
-                                                     C.c_void_p(0), None, 1 if last else 0,
-                                                     _ptr(e_emb if layer > 0 else None), _ptr(e_emb if layer == 0 else None),
-                                                     C.c_void_p(0), _ptr(None if last else h2), _ptr(out), st),
-                               "cgvp_conv_layer_fwd")
+                _lib.check(L.cgvp_conv_layer_fwd(d, lay, I, layer, _ptr(h), _ptr(e_s), _ptr(e_v), _ptr(et),
+                                                 _ptr(csr.rowptr), _ptr(csr.eperm), _ptr(csr.esrc),
+                                                 _ptr(csr.edst), N, E, 1 if aggr_mean else 0, C.c_void_p(0),
+                                                 C.c_void_p(0), None, 1 if last else 0,
+                                                 _ptr(e_emb if layer > 0 else None), _ptr(e_emb if layer == 0 else None),
+                                                 C.c_void_p(0), _ptr(None if last else h2), _ptr(out), st),
+                           "cgvp_conv_layer_fwd")
                 if not last:
                     h, h2 = h2, h
                 continue
-            with _timed("conv_fwd"):
-                _lib.check(L.cgvp_conv_fwd(d, lay, P, I, layer, _ptr(h), _ptr(e_s), _ptr(e_v), _ptr(et),
-                                           _ptr(csr.rowptr), _ptr(csr.eperm), _ptr(csr.esrc), _ptr(csr.edst),
-                                           N, E, 1 if aggr_mean else 0, _ptr(e_emb if layer > 0 else None),
-                                           _ptr(e_emb if layer == 0 else None), _ptr(dh), st), "cgvp_conv_fwd")
+            _lib.check(L.cgvp_conv_fwd(d, lay, P, I, layer, _ptr(h), _ptr(e_s), _ptr(e_v), _ptr(et),
+                                       _ptr(csr.rowptr), _ptr(csr.eperm), _ptr(csr.esrc), _ptr(csr.edst),
+                                       N, E, 1 if aggr_mean else 0, _ptr(e_emb if layer > 0 else None),
+                                       _ptr(e_emb if layer == 0 else None), _ptr(dh), st), "cgvp_conv_fwd")
             if return_stages:
                 stages[f"conv{layer}_dh"] = dh.clone()
             last = layer == num_convs - 1
