@@ -66,7 +66,7 @@ int32_t bwd_flags() { return at::globalContext().deterministicAlgorithms() ? CGV
 // rc of call(flags); a path without a deterministic form returns CGVP_ERR_NONDETERMINISTIC before it launches anything:
 // under use_deterministic_algorithms(True, warn_only=True) it is warned about and run in the default mode
 template <class F>
-int call_bwd(F call, int32_t flags, const char* what) {
+int call_bwd(const F& call, int32_t flags, const char* what) {
   int rc = call(flags);
   if (rc == CGVP_ERR_NONDETERMINISTIC && flags && !cgvp_deterministic_forced() &&
       at::globalContext().deterministicAlgorithmsWarnOnly()) {
@@ -177,16 +177,11 @@ struct Guarded { at::Tensor t; int64_t version; const char* what; };
 inline void guard_add(std::vector<Guarded>& g, const at::Tensor& t, const char* what) {
   if (t.defined() && !t.is_inference()) g.push_back({t, t._version(), what});
 }
-inline void guard_check(const std::vector<Guarded>& g, const char* node) {
+inline void guard_check(const std::vector<Guarded>& g, const char* encoder) {
   for (const Guarded& e : g)
-    TORCH_CHECK(e.t._version() == e.version, "caster_gvp: ", e.what, " needed by ", node, " was modified by an in-place "
-                "operation after the forward pass (version ", e.version, " -> ", e.t._version(), "): the gradients would be "
-                "computed from the new values");
-}
-// The kernels' backward is not itself differentiable: create_graph=True must fail loudly instead of returning constants.
-inline void once_differentiable(const char* node) {
-  TORCH_CHECK(!at::GradMode::is_enabled(), "caster_gvp: ", node, " is not differentiable twice (backward called with "
-              "create_graph=True); the encoder kernels provide first derivatives only");
+    TORCH_CHECK(e.t._version() == e.version, "caster_gvp: ", e.what, " needed by the ", encoder, " encoder's backward "
+                "was modified by an in-place operation after the forward pass (version ", e.version, " -> ", e.t._version(),
+                "): the gradients would be computed from the new values");
 }
 
 at::Tensor ready(const at::Tensor& t, const char* name, c10::optional<at::ScalarType> dtype = c10::nullopt) {
@@ -251,84 +246,162 @@ at::Tensor flat_arena(const std::vector<at::Tensor>& params, bool* zero_copy) {
   return at::cat(flat);
 }
 
-struct Tables { const int32_t* rowptr = nullptr; const int32_t* eperm = nullptr; const int32_t* esrc = nullptr; const int32_t* edst = nullptr; };
-Tables tables_of(const std::vector<at::Tensor>& csr) {
-  Tables t;
-  if (csr.empty()) return t;
+// A pass's batch struct with the prebuilt CSR tables `csr` = [rowptr, eperm, esrc, edst] (or []: the pass builds them)
+template <class Batch>
+Batch with_tables(Batch b, const std::vector<at::Tensor>& csr) {
+  if (csr.empty()) return b;
   TORCH_CHECK(csr.size() == 4, "csr must be [] or [rowptr, eperm, esrc, edst]");
   for (const at::Tensor& c : csr) TORCH_CHECK(c.is_cuda() && c.scalar_type() == at::kInt && c.is_contiguous(), "csr tables must be contiguous int32 CUDA tensors");
-  t.rowptr = csr[0].data_ptr<int32_t>(); t.eperm = csr[1].data_ptr<int32_t>();
-  t.esrc = csr[2].data_ptr<int32_t>(); t.edst = csr[3].data_ptr<int32_t>();
-  return t;
+  b.rowptr = csr[0].data_ptr<int32_t>(); b.eperm = csr[1].data_ptr<int32_t>();
+  b.esrc = csr[2].data_ptr<int32_t>(); b.edst = csr[3].data_ptr<int32_t>();
+  return b;
 }
 
-// ===================================================================================== protein encoder
-struct LbaBackward : public Node {
-  LbaCfg cfg;
-  at::Tensor x_s, x_v, ntypes, e_s, e_v, etypes, ws, masks;
+// ===================================================================================== both encoder passes
+// Where a forward pass's dropout factors come from: nowhere (p = 0: inference, or a pass without dropout sites), the
+// caller's pinned masks (a test hook), or a draw from the persistent generator state.  `p` is what the backward applies.
+struct Dropout { double p; bool pinned, draw; };
+Dropout dropout_source(double p, bool save_state, bool has_sites, bool masks_given,
+                       const c10::optional<at::Tensor>& rng_state) {
+  const bool drop = p > 0 && save_state && has_sites;
+  const Dropout d{drop ? p : 0.0, drop && masks_given, drop && !masks_given};
+  TORCH_CHECK(!d.draw || rng_state, "training-mode dropout needs the persistent generator state");
+  return d;
+}
+// The persistent counters the pass builds the CSR in, or nullptr when `csr` brings the tables.
+int32_t* csr_counters(const std::vector<at::Tensor>& csr, const c10::optional<at::Tensor>& counters) {
+  TORCH_CHECK(!csr.empty() || counters, "the CSR build needs the persistent counters");
+  return csr.empty() ? (int32_t*)ptr(counters) : nullptr;
+}
+void check_forward(int rc, c10::optional<at::Tensor>& counters, const char* what) {
+  if (rc != 0 && counters) counters->zero_();     // the persistent counters must not stay half-used
+  check(rc, what);
+}
+
+// What every pass's backward needs from its forward.
+struct PassSaved {
+  at::Tensor ws;                    // the forward workspace; undefined once the node's variables are released
   std::vector<at::Tensor> csr;
-  std::vector<std::vector<int64_t>> shapes, strides;
-  std::vector<int64_t> numels;
-  at::ScalarType x_dtype;
   int64_t N = 0, E = 0;
   double dropout_p = 0;
+};
+// A contiguous gradient of one parameter inside the gradient arena, recorded at forward time.
+struct ParamSlot { at::DimVector sizes, strides; int64_t offset; };
+// What a pass's node is reported as: the node, the encoder (in messages), its Tic sections and its two C functions.
+struct PassNames { const char *node, *encoder, *apply, *call, *views, *ws_query, *bwd; };
+
+// The autograd node of one encoder pass: apply() runs the backward pass and returns the parameter gradients as views of
+// ONE gradient arena, then the input gradients.  `Pass` (CRTP) adds what only it saves, and supplies kNames;
+// InputGrads, a std::array; workspace_bytes(flags), its *_bwd_workspace_bytes_ex query; input_grads(f32), the fp32
+// input-gradient buffers, and input_grad(g), one as it is returned; backward_call(g_out, bws, garena, g_in), a
+// callable f(flags) -> rc that runs its *_backward_pass_ex.
+template <class Pass>
+struct EncoderBackward : public Node, PassSaved {
+  std::vector<ParamSlot> slots;     // one per parameter leaf the forward was given (one_leaf: the arena itself)
+  int64_t arena_numel = 0;
   bool need_x = false;
+  bool one_leaf = false;            // the single leaf is the flat arena: it gets the arena itself, LeafScatter stays out
   std::vector<Guarded> guarded;
 
   variable_list apply(variable_list&& grads) override {
-    Tic tic_all("lba_bwd.apply");
-    once_differentiable("CasterGvpLbaEncoderBackward");
-    const size_t np = shapes.size();
-    variable_list out(np + 2);
+    constexpr PassNames names = Pass::kNames;
+    Tic tic_all(names.apply);
+    // The kernels' backward is not itself differentiable: create_graph=True must fail loudly instead of returning constants.
+    TORCH_CHECK(!at::GradMode::is_enabled(), "caster_gvp: ", names.node, " is not differentiable twice (backward called "
+                "with create_graph=True); the encoder kernels provide first derivatives only");
+    const size_t np = slots.size(), ni = std::tuple_size_v<typename Pass::InputGrads>;
+    variable_list out(np + ni);
     if (grads.empty() || !grads[0].defined()) return out;
-    TORCH_CHECK(ws.defined(), "caster_gvp: backward through a protein encoder pass whose saved state was already released "
-                              "(call backward once, or pass retain_graph=True)");
-    guard_check(guarded, "the protein encoder's backward");
-    c10::DeviceGuard guard(x_s.device());
+    TORCH_CHECK(ws.defined(), "caster_gvp: backward through a ", names.encoder, " encoder pass whose saved state was "
+                "already released (call backward once, or pass retain_graph=True)");
+    guard_check(guarded, names.encoder);
+    c10::DeviceGuard guard(ws.device());
     at::Tensor g_out = ready(grads[0], "grad_output", at::kFloat);
-    auto f32 = x_s.options().dtype(at::kFloat).requires_grad(false);
-    at::Tensor gparams = at::empty({(int64_t)cfg.layout.total}, f32);
+    auto f32 = ws.options().dtype(at::kFloat).requires_grad(false);
+    at::Tensor garena = at::empty({arena_numel}, f32);
+    Pass& pass = static_cast<Pass&>(*this);
     const int32_t flags = bwd_flags();
-    const int64_t nbytes = cgvp_lba_bwd_workspace_bytes_ex(&cfg.dims, &cfg.layout, N, E, flags);
-    if (nbytes < 0) check((int)nbytes, "cgvp_lba_bwd_workspace_bytes_ex");
+    const int64_t nbytes = pass.workspace_bytes(flags);
+    if (nbytes < 0) check((int)nbytes, names.ws_query);
     at::Tensor bws = at::empty({nbytes}, f32.dtype(at::kByte));
-    at::Tensor g_x_s, g_x_v;
-    if (need_x) {
-      g_x_s = at::empty({N, (int64_t)cfg.dims.node_in_s}, f32);
-      g_x_v = at::empty({N, (int64_t)cfg.dims.node_in_v, 3}, f32);
-    }
-    const Tables t = tables_of(csr);
-    cgvp_lba_batch b{N, E, (const float*)ptr(x_s), (const float*)ptr(x_v), (const int64_t*)ptr(ntypes),
-                     (const float*)ptr(e_s), (const float*)ptr(e_v), (const int64_t*)ptr(etypes), nullptr,
-                     t.rowptr, t.eperm, t.esrc, t.edst};
+    typename Pass::InputGrads g_in;
+    if (need_x) g_in = pass.input_grads(f32);
+    auto call = pass.backward_call(g_out, bws, garena, g_in);
     {
-      Tic tic_c("lba_bwd.c_call");
-      check(call_bwd([&](int32_t f) {
-              return cgvp_lba_backward_pass_ex(&cfg.dims, &cfg.layout, &b, cfg.mean, (float)dropout_p, (const float*)ptr(masks),
-                                               ptr(ws), (const float*)ptr(g_out), ptr(bws), (float*)ptr(gparams),
-                                               (float*)ptr(g_x_s), (float*)ptr(g_x_v), nullptr, nullptr, f, current_stream(x_s));
-            }, flags, "cgvp_lba_backward_pass_ex"),
-            "cgvp_lba_backward_pass_ex");
+      Tic tic_c(names.call);
+      check(call_bwd(call, flags, names.bwd), names.bwd);
     }
-    Tic tic_v("lba_bwd.views");
-    int64_t off = 0;
-    for (size_t i = 0; i < np; ++i) {      // one view op per parameter (as_strided), not narrow + view
-      if (task_should_compute_output(i)) out[i] = arena_view(gparams, shapes[i], strides[i], off);
-      off += numels[i];
+    Tic tic_v(names.views);
+    if (one_leaf) {
+      if (task_should_compute_output(0)) out[0] = garena;
+    } else {
+      for (size_t i = 0; i < np; ++i)      // one view op per parameter (as_strided), not narrow + view
+        if (task_should_compute_output(i)) out[i] = arena_view(garena, slots[i].sizes, slots[i].strides, slots[i].offset);
+      if (LeafScatter::run(*this, np, out, garena))
+        for (size_t i = 0; i < np; ++i) out[i] = at::Tensor();
     }
-    if (LeafScatter::run(*this, np, out, gparams))
-      for (size_t i = 0; i < np; ++i) out[i] = at::Tensor();
-    if (need_x) {
-      out[np] = x_dtype == at::kFloat ? g_x_s : g_x_s.to(x_dtype);
-      out[np + 1] = x_dtype == at::kFloat ? g_x_v : g_x_v.to(x_dtype);
-    }
+    if (need_x)
+      for (size_t i = 0; i < ni; ++i) out[np + i] = pass.input_grad(g_in[i]);
     return out;
   }
   void release_variables() override {
-    ws.reset(); masks.reset(); x_s.reset(); x_v.reset(); e_s.reset(); e_v.reset(); ntypes.reset(); etypes.reset();
-    csr.clear(); guarded.clear();
+    ws.reset(); csr.clear(); guarded.clear();
+    static_cast<Pass&>(*this).release_inputs();
   }
-  std::string name() const override { return "CasterGvpLbaEncoderBackward"; }
+  std::string name() const override { return Pass::kNames.node; }
+};
+
+// The backward node of a training pass, attached to `out`; nullptr when neither a parameter nor an input needs a
+// gradient.  Its edges lead to `params`, then to `inputs` (the caller's tensors, before ready()); the backward re-reads
+// `guard` from live storage.  The caller then fills in what only its pass saves.
+template <class Pass, class... In>
+Pass* attach_node(at::Tensor& out, const std::vector<at::Tensor>& params, bool one_leaf, PassSaved saved,
+                  std::initializer_list<std::pair<const at::Tensor&, const char*>> guard, const In&... inputs) {
+  bool any = false;
+  for (const at::Tensor& p : params) any = any || p.requires_grad();
+  const bool need_x = (inputs.requires_grad() || ...);
+  if (!at::GradMode::is_enabled() || !(any || need_x)) return nullptr;
+  auto node = std::shared_ptr<Pass>(new Pass(), torch::autograd::deleteNode);
+  node->set_next_edges(torch::autograd::collect_next_edges(params, inputs...));
+  static_cast<PassSaved&>(*node) = std::move(saved);
+  node->need_x = need_x;
+  node->one_leaf = one_leaf;
+  node->slots.reserve(params.size());
+  for (const at::Tensor& p : params) {
+    node->slots.push_back({at::DimVector(p.sizes()), c10::contiguous_strides(p.sizes()), node->arena_numel});
+    node->arena_numel += p.numel();
+  }
+  for (const auto& g : guard) guard_add(node->guarded, g.first, g.second);
+  torch::autograd::set_history(out, node);
+  return node.get();
+}
+
+// ===================================================================================== protein encoder
+struct LbaBackward : public EncoderBackward<LbaBackward> {
+  static constexpr PassNames kNames{"CasterGvpLbaEncoderBackward", "protein", "lba_bwd.apply", "lba_bwd.c_call",
+                                    "lba_bwd.views", "cgvp_lba_bwd_workspace_bytes_ex", "cgvp_lba_backward_pass_ex"};
+  using InputGrads = std::array<at::Tensor, 2>;     // g_x_s, g_x_v
+
+  LbaCfg cfg;
+  at::Tensor x_s, x_v, ntypes, e_s, e_v, etypes, masks;
+  at::ScalarType x_dtype;
+
+  int64_t workspace_bytes(int32_t flags) const { return cgvp_lba_bwd_workspace_bytes_ex(&cfg.dims, &cfg.layout, N, E, flags); }
+  InputGrads input_grads(const at::TensorOptions& f32) const {
+    return {at::empty({N, (int64_t)cfg.dims.node_in_s}, f32), at::empty({N, (int64_t)cfg.dims.node_in_v, 3}, f32)};
+  }
+  at::Tensor input_grad(const at::Tensor& g) const { return x_dtype == at::kFloat ? g : g.to(x_dtype); }
+  auto backward_call(const at::Tensor& g_out, const at::Tensor& bws, const at::Tensor& garena, const InputGrads& g_in) {
+    const cgvp_lba_batch b = with_tables(cgvp_lba_batch{N, E, (const float*)ptr(x_s), (const float*)ptr(x_v),
+                                                        (const int64_t*)ptr(ntypes), (const float*)ptr(e_s),
+                                                        (const float*)ptr(e_v), (const int64_t*)ptr(etypes)}, csr);
+    return [this, b, &g_out, &bws, &garena, &g_in](int32_t f) {
+      return cgvp_lba_backward_pass_ex(&cfg.dims, &cfg.layout, &b, cfg.mean, (float)dropout_p, (const float*)ptr(masks),
+                                       ptr(ws), (const float*)ptr(g_out), ptr(bws), (float*)ptr(garena),
+                                       (float*)ptr(g_in[0]), (float*)ptr(g_in[1]), nullptr, nullptr, f, current_stream(x_s));
+    };
+  }
+  void release_inputs() { masks.reset(); x_s.reset(); x_v.reset(); e_s.reset(); e_v.reset(); ntypes.reset(); etypes.reset(); }
 };
 
 // -> (out [N, out_s], ws: the forward workspace (uint8; undefined when the pass saved nothing), whether the parameters
@@ -360,54 +433,32 @@ std::tuple<at::Tensor, at::Tensor, bool> lba_encoder(std::vector<at::Tensor> par
   bool zero_copy = false;
   at::Tensor flat = flat_arena(params, &zero_copy);
   TORCH_CHECK(flat.numel() == cfg.layout.total, "parameter arena has ", flat.numel(), " floats, kernels expect ", cfg.layout.total);
-  const bool drop = dropout_p > 0 && save_state;
-  const bool draw = drop && !(masks && masks->numel() > 0);
-  TORCH_CHECK(!draw || rng_state, "training-mode dropout needs the persistent generator state");
-  TORCH_CHECK(tables || counters, "the CSR build needs the persistent counters");
+  const Dropout d = dropout_source(dropout_p, save_state, true, masks && masks->numel() > 0, rng_state);
+  int32_t* cnt = csr_counters(csr, counters);
   c10::DeviceGuard guard(x_s.device());
   cgvp_lba_fwd_ws wsd;
   check(cgvp_lba_fwd_workspace(&cfg.dims, &cfg.layout, N, E, save_state ? 1 : 0, &wsd), "cgvp_lba_fwd_workspace");
   auto opts = x_s.options().requires_grad(false);
   at::Tensor ws = at::empty({wsd.total}, opts.dtype(at::kByte));
   at::Tensor out = at::empty({N, (int64_t)cfg.dims.out_s}, opts.dtype(sdt));
-  const Tables t = tables_of(csr);
-  cgvp_lba_batch b{N, E, (const float*)ptr(x_s), (const float*)ptr(x_v), (const int64_t*)ptr(ntypes),
-                   (const float*)ptr(e_s), (const float*)ptr(e_v), (const int64_t*)ptr(etypes),
-                   (const int64_t*)ptr(edge_index), t.rowptr, t.eperm, t.esrc, t.edst};
+  const cgvp_lba_batch b = with_tables(cgvp_lba_batch{N, E, (const float*)ptr(x_s), (const float*)ptr(x_v),
+                                                      (const int64_t*)ptr(ntypes), (const float*)ptr(e_s),
+                                                      (const float*)ptr(e_v), (const int64_t*)ptr(etypes),
+                                                      (const int64_t*)ptr(edge_index)}, csr);
   Tic tic_f("lba_fwd.c_call");
   const int rc = cgvp_lba_forward_pass(&cfg.dims, &cfg.layout, (const float*)ptr(flat), &b, cfg.mean,
-                                       save_state ? (float)dropout_p : 0.f, draw ? (uint64_t*)ptr(rng_state) : nullptr,
-                                       drop ? (const float*)ptr(masks) : nullptr, tables ? nullptr : (int32_t*)ptr(counters),
-                                       ptr(ws), save_state ? 1 : 0, fuse ? 0 : CGVP_PASS_UNFUSED, (float*)ptr(out),
-                                       current_stream(x_s));
-  if (rc != 0 && counters) counters->zero_();     // the persistent counters must not stay half-used
-  check(rc, "cgvp_lba_forward_pass");
+                                       save_state ? (float)dropout_p : 0.f, d.draw ? (uint64_t*)ptr(rng_state) : nullptr,
+                                       d.pinned ? (const float*)ptr(masks) : nullptr, cnt, ptr(ws), save_state ? 1 : 0,
+                                       fuse ? 0 : CGVP_PASS_UNFUSED, (float*)ptr(out), current_stream(x_s));
+  check_forward(rc, counters, "cgvp_lba_forward_pass");
   if (!save_state) return {out, at::Tensor(), zero_copy};
-  // autograd: one node for the whole pass
-  bool any = false;
-  for (const at::Tensor& p : params) any = any || p.requires_grad();
-  const bool need_x = x_s_in.requires_grad() || x_v_in.requires_grad();
-  if (at::GradMode::is_enabled() && (any || need_x)) {
-    auto node = std::shared_ptr<LbaBackward>(new LbaBackward(), torch::autograd::deleteNode);
-    torch::autograd::edge_list edges = torch::autograd::collect_next_edges(params, x_s_in, x_v_in);
-    node->set_next_edges(std::move(edges));
+  if (LbaBackward* node = attach_node<LbaBackward>(out, params, false, {ws, std::move(csr), N, E, d.p},
+                                                   {{x_s, "x_s"}, {x_v, "x_v"}, {e_s, "eattr_s"}, {e_v, "eattr_v"}},
+                                                   x_s_in, x_v_in)) {
     node->cfg = cfg;
     node->x_s = x_s; node->x_v = x_v; node->ntypes = ntypes; node->e_s = e_s; node->e_v = e_v; node->etypes = etypes;
-    node->ws = ws;
-    if (drop && masks && masks->numel() > 0) node->masks = *masks;
-    node->csr = csr;
-    node->N = N; node->E = E; node->dropout_p = drop ? dropout_p : 0.0; node->need_x = need_x;
+    if (d.pinned) node->masks = *masks;
     node->x_dtype = x_s_in.scalar_type();
-    guard_add(node->guarded, x_s, "x_s"); guard_add(node->guarded, x_v, "x_v");
-    guard_add(node->guarded, e_s, "eattr_s"); guard_add(node->guarded, e_v, "eattr_v");
-    node->shapes.reserve(params.size());
-    node->strides.reserve(params.size());
-    for (const at::Tensor& p : params) {
-      node->shapes.push_back(p.sizes().vec());
-      { auto st = c10::contiguous_strides(p.sizes()); node->strides.emplace_back(st.begin(), st.end()); }
-      node->numels.push_back(p.numel());
-    }
-    torch::autograd::set_history(out, node);
   }
   return {out, ws, zero_copy};
 }
@@ -464,75 +515,37 @@ void gine_weights(const std::vector<at::Tensor>& params, int L, std::vector<at::
   }
 }
 
-struct GineBackward : public Node {
-  GineMeta meta;
-  std::vector<at::Tensor> params, csr, masks;
-  at::Tensor x, ntypes, eattr, etypes, ws;
-  int64_t N = 0, E = 0;
-  double dropout_p = 0;
-  bool need_x = false;
-  bool one_leaf = false;          // the caller's `params` was the single fused arena: return one gradient
-  int max_workgroups = 0;
-  std::vector<Guarded> guarded;
+struct GineBackward : public EncoderBackward<GineBackward> {
+  static constexpr PassNames kNames{"CasterGvpGineEncoderBackward", "drug", "gine_bwd.apply", "gine_bwd.c_call",
+                                    "gine_bwd.views", "cgvp_gine_bwd_workspace_bytes_ex", "cgvp_gine_backward_pass_ex"};
+  using InputGrads = std::array<at::Tensor, 1>;     // g_x
 
-  variable_list apply(variable_list&& grads) override {
-    Tic tic_all("gine_bwd.apply");
-    once_differentiable("CasterGvpGineEncoderBackward");
-    const size_t np = one_leaf ? 1 : params.size();
-    variable_list out(np + 1);
-    if (grads.empty() || !grads[0].defined()) return out;
-    TORCH_CHECK(ws.defined(), "caster_gvp: backward through a drug encoder pass whose saved state was already released "
-                              "(call backward once, or pass retain_graph=True)");
-    guard_check(guarded, "the drug encoder's backward");
-    c10::DeviceGuard guard(x.device());
-    at::Tensor g_out = ready(grads[0], "grad_output", at::kFloat);
-    auto f32 = x.options().dtype(at::kFloat).requires_grad(false);
-    int64_t total = 0;
-    for (const at::Tensor& p : params) total += p.numel();
-    at::Tensor gflat = at::empty({total}, f32);
-    const int32_t flags = bwd_flags();
-    const int64_t nbytes = cgvp_gine_bwd_workspace_bytes_ex(&meta.cfg, N, E, flags);
-    if (nbytes < 0) check((int)nbytes, "cgvp_gine_bwd_workspace_bytes_ex");
-    at::Tensor bws = at::empty({nbytes}, f32.dtype(at::kByte));
-    at::Tensor g_x;
-    if (need_x) g_x = at::empty({N, (int64_t)(meta.cfg.widths[0] - meta.cfg.num_ntypes)}, f32);
+  GineMeta meta;
+  std::vector<at::Tensor> params, masks;    // the 7 L kernel tensors (views of the arena in one-leaf mode)
+  at::Tensor x, ntypes, eattr, etypes;
+  int max_workgroups = 0;
+
+  int64_t workspace_bytes(int32_t flags) const { return cgvp_gine_bwd_workspace_bytes_ex(&meta.cfg, N, E, flags); }
+  InputGrads input_grads(const at::TensorOptions& f32) const {
+    return {at::empty({N, (int64_t)(meta.cfg.widths[0] - meta.cfg.num_ntypes)}, f32)};
+  }
+  at::Tensor input_grad(const at::Tensor& g) const { return g; }
+  auto backward_call(const at::Tensor& g_out, const at::Tensor& bws, const at::Tensor& garena, const InputGrads& g_in) {
     std::vector<at::Tensor> keep;
     std::vector<cgvp_gine_w> w;
     gine_weights(params, meta.L, keep, w);
-    const Tables t = tables_of(csr);
-    cgvp_gine_batch b{N, E, (const float*)ptr(x), (const int64_t*)ptr(ntypes), (const float*)ptr(eattr),
-                      (const int64_t*)ptr(etypes), nullptr, t.rowptr, t.eperm, t.esrc, t.edst};
+    const cgvp_gine_batch b = with_tables(cgvp_gine_batch{N, E, (const float*)ptr(x), (const int64_t*)ptr(ntypes),
+                                                          (const float*)ptr(eattr), (const int64_t*)ptr(etypes)}, csr);
     std::vector<const float*> mp;
     for (const at::Tensor& m : masks) mp.push_back((const float*)ptr(m));
-    {
-      Tic tic_c("gine_bwd.c_call");
-      check(call_bwd([&](int32_t f) {
-              return cgvp_gine_backward_pass_ex(&meta.cfg, w.data(), &b, (float)dropout_p, mp.empty() ? nullptr : mp.data(),
-                                                ptr(ws), (const float*)ptr(g_out), ptr(bws), (float*)ptr(gflat), (float*)ptr(g_x),
-                                                max_workgroups, f, current_stream(x));
-            }, flags, "cgvp_gine_backward_pass_ex"),
-            "cgvp_gine_backward_pass_ex");
-    }
-    if (one_leaf) {
-      if (task_should_compute_output(0)) out[0] = gflat;
-    } else {
-      int64_t off = 0;
-      for (size_t i = 0; i < np; ++i) {
-        const int64_t n = params[i].numel();
-        if (task_should_compute_output(i)) out[i] = arena_view(gflat, params[i].sizes(), c10::contiguous_strides(params[i].sizes()), off);
-        off += n;
-      }
-      if (LeafScatter::run(*this, np, out, gflat))
-        for (size_t i = 0; i < np; ++i) out[i] = at::Tensor();
-    }
-    if (need_x) out[np] = g_x;
-    return out;
+    // (`keep` holds the weights the pointers in `w` point into)
+    return [this, keep = std::move(keep), w = std::move(w), mp = std::move(mp), b, &g_out, &bws, &garena, &g_in](int32_t f) {
+      return cgvp_gine_backward_pass_ex(&meta.cfg, w.data(), &b, (float)dropout_p, mp.empty() ? nullptr : mp.data(),
+                                        ptr(ws), (const float*)ptr(g_out), ptr(bws), (float*)ptr(garena),
+                                        (float*)ptr(g_in[0]), max_workgroups, f, current_stream(x));
+    };
   }
-  void release_variables() override {
-    ws.reset(); x.reset(); eattr.reset(); ntypes.reset(); etypes.reset(); params.clear(); csr.clear(); masks.clear();
-    guarded.clear();
-  }
-  std::string name() const override { return "CasterGvpGineEncoderBackward"; }
+  void release_inputs() { x.reset(); eattr.reset(); ntypes.reset(); etypes.reset(); params.clear(); masks.clear(); }
 };
 
 std::tuple<at::Tensor, at::Tensor> gine_encoder(std::vector<at::Tensor> params_in, at::Tensor x_in, at::Tensor ntypes_in,
@@ -549,62 +562,47 @@ std::tuple<at::Tensor, at::Tensor> gine_encoder(std::vector<at::Tensor> params_i
   const int64_t N = x.size(0), E = edge_index_in.size(1);
   const GineMeta meta = gine_meta(widths, num_ntypes, num_etypes, eattr.size(1), slope);
   if (x.size(1) != widths[0] - num_ntypes) throw py::value_error("x has " + std::to_string(x.size(1)) + " columns, expected " + std::to_string(widths[0] - num_ntypes));
-  const bool tables = !csr.empty();
   at::Tensor ntypes, etypes, edge_index;
   if (num_ntypes > 0) ntypes = ready(ntypes_in, "ntypes", at::kLong);
   if (num_etypes > 0) etypes = ready(etypes_in, "etypes", at::kLong);
-  if (!tables) edge_index = ready(edge_index_in, "edge_index", at::kLong);
+  if (csr.empty()) edge_index = ready(edge_index_in, "edge_index", at::kLong);
   const bool one_leaf = params_in.size() == 1;
   const std::vector<at::Tensor> params = one_leaf ? gine_split_arena(params_in[0], meta) : params_in;
   std::vector<at::Tensor> keep;
   std::vector<cgvp_gine_w> w;
   gine_weights(params, meta.L, keep, w);
-  const bool drop = dropout_p > 0 && save_state && meta.L > 1;
-  const bool pinned = drop && !masks.empty();
-  const bool draw = drop && !pinned;
-  TORCH_CHECK(!draw || rng_state, "training-mode dropout needs the persistent generator state");
-  TORCH_CHECK(tables || counters, "the CSR build needs the persistent counters");
+  const Dropout d = dropout_source(dropout_p, save_state, meta.L > 1, !masks.empty(), rng_state);
+  int32_t* cnt = csr_counters(csr, counters);
   c10::DeviceGuard guard(x.device());
   cgvp_gine_fwd_ws wsd;
   check(cgvp_gine_fwd_workspace(&meta.cfg, N, E, save_state ? 1 : 0, &wsd), "cgvp_gine_fwd_workspace");
   auto opts = x.options().requires_grad(false);
   at::Tensor ws = at::empty({wsd.total}, opts.dtype(at::kByte));
   at::Tensor out = at::empty({N, widths.back()}, opts);
-  const Tables t = tables_of(csr);
-  cgvp_gine_batch b{N, E, (const float*)ptr(x), (const int64_t*)ptr(ntypes), (const float*)ptr(eattr),
-                    (const int64_t*)ptr(etypes), (const int64_t*)ptr(edge_index), t.rowptr, t.eperm, t.esrc, t.edst};
+  const cgvp_gine_batch b = with_tables(cgvp_gine_batch{N, E, (const float*)ptr(x), (const int64_t*)ptr(ntypes),
+                                                        (const float*)ptr(eattr), (const int64_t*)ptr(etypes),
+                                                        (const int64_t*)ptr(edge_index)}, csr);
   std::vector<const float*> mp;
-  if (pinned) {
+  if (d.pinned) {
     TORCH_CHECK((int)masks.size() == meta.L - 1, "expected one mask per layer but the last");
     for (at::Tensor& m : masks) { m = ready(m, "mask", at::kFloat); mp.push_back((const float*)ptr(m)); }
   }
   const int rc = cgvp_gine_forward_pass(&meta.cfg, w.data(), &b, save_state ? (float)dropout_p : 0.f,
-                                        draw ? (uint64_t*)ptr(rng_state) : nullptr, pinned ? mp.data() : nullptr,
-                                        tables ? nullptr : (int32_t*)ptr(counters), ptr(ws), save_state ? 1 : 0, (int32_t)variant,
-                                        (float*)ptr(out), current_stream(x));
-  if (rc != 0 && counters) counters->zero_();
-  check(rc, "cgvp_gine_forward_pass");
+                                        d.draw ? (uint64_t*)ptr(rng_state) : nullptr, d.pinned ? mp.data() : nullptr, cnt,
+                                        ptr(ws), save_state ? 1 : 0, (int32_t)variant, (float*)ptr(out), current_stream(x));
+  check_forward(rc, counters, "cgvp_gine_forward_pass");
   if (!save_state) return {out, at::Tensor()};
-  bool any = false;
-  for (const at::Tensor& p : params_in) any = any || p.requires_grad();
-  const bool need_x = x_in.requires_grad();
-  if (at::GradMode::is_enabled() && (any || need_x)) {
-    auto node = std::shared_ptr<GineBackward>(new GineBackward(), torch::autograd::deleteNode);
-    node->set_next_edges(torch::autograd::collect_next_edges(params_in, x_in));
+  if (GineBackward* node = attach_node<GineBackward>(out, params_in, one_leaf, {ws, std::move(csr), N, E, d.p},
+                                                     {{x, "x"}, {eattr, "eattr"}}, x_in)) {
     node->meta = meta;
-    node->one_leaf = one_leaf;
     node->params.reserve(params.size());
     for (const at::Tensor& p : params) {
       node->params.push_back(p.detach());
       guard_add(node->guarded, node->params.back(), "a drug-encoder weight");     // (detach() shares the version counter)
     }
-    node->csr = csr;
-    if (pinned) node->masks = masks;
-    node->x = x; node->ntypes = ntypes; node->eattr = eattr; node->etypes = etypes; node->ws = ws;
-    node->N = N; node->E = E; node->dropout_p = drop ? dropout_p : 0.0; node->need_x = need_x;
+    if (d.pinned) node->masks = std::move(masks);
+    node->x = x; node->ntypes = ntypes; node->eattr = eattr; node->etypes = etypes;
     node->max_workgroups = (int)bwd_workgroups;
-    guard_add(node->guarded, x, "x"); guard_add(node->guarded, eattr, "eattr");
-    torch::autograd::set_history(out, node);
   }
   return {out, ws};
 }

@@ -33,6 +33,7 @@ generation alive, `rng_state` re-seeds in place).
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import List, Tuple
 
@@ -172,12 +173,84 @@ def _csr_ptrs(csr):
     return tuple(t.data_ptr() for t in csr)
 
 
-def _lba_batch(x_s, x_v, nt, e_s, e_v, et, edge_index, csr, N, E):
-    rp, ep, es_, ed = _csr_ptrs(csr)
-    return _lib.LbaBatch(N, E, x_s.data_ptr(), x_v.data_ptr(), nt.data_ptr() if nt is not None else 0,
-                         e_s.data_ptr() if E > 0 else 0, e_v.data_ptr() if E > 0 else 0,
-                         et.data_ptr() if (et is not None and E > 0) else 0,
-                         edge_index.data_ptr() if (E > 0 and not csr) else 0, rp, ep, es_, ed)
+def _batch(cls, nodes, edges, edge_index, csr, N, E):
+    """A batch struct (_lib.LbaBatch / _lib.GineBatch): N, E, the pointers of the node tensors, of the edge tensors
+    (NULL without edges), of edge_index (NULL when `csr` brings the tables) and of the four tables.  None: NULL."""
+    ptr = lambda t: 0 if t is None else t.data_ptr()
+    return cls(N, E, *map(ptr, nodes), *(ptr(t) if E > 0 else 0 for t in edges),
+               ptr(edge_index) if (E > 0 and not csr) else 0, *_csr_ptrs(csr))
+
+
+# ------------------------------------------------------------------------------------- what both encoders share
+def _dropout(p, save_state, shapes, dev):
+    """(masks from the PINNED_MASKS test hook, one per (count, N, width) in `shapes`, or None; whether the pass draws
+    from the persistent generator state instead).  A pass without dropout sites has no `shapes`."""
+    if p <= 0 or not save_state or not shapes:
+        return None, False
+    if PINNED_MASKS is None:
+        return None, True
+    return [PINNED_MASKS(count, n, width, p, dev) for count, n, width in shapes], False
+
+
+def _record_draw(kind, ws, draw):
+    """A pass that drew its dropout factors left its {seed, offset} pair at the start of `ws` (last_seed reads it)."""
+    if draw:
+        _LAST_WS[kind] = (ws, 0)
+
+
+def _forward_pass(kind, what, call, ws, draw, csr, N):
+    """Run the forward entry point `what` as call(counters) -> rc on ws's device; `counters`: the persistent CSR
+    counters, or None when `csr` brings the tables."""
+    dev = ws.device
+    with torch.cuda.device(dev):
+        counters = ops.csr_counters(dev, N) if not csr else None
+        rc = call(counters)
+    if rc != 0 and counters is not None:
+        counters.zero_()               # the persistent counters must not stay half-used (the next build assumes zeros)
+    _lib.check(rc, what)
+    _record_draw(kind, ws, draw)
+
+
+def _backward_pass(query, args, what, call, ws):
+    """Run the backward entry point `what` as call(ws, scratch, flags) -> rc in the mode torch is in now; its workspace
+    query(*args, flags) sizes the scratch (< 0: an error code).  The saved forward workspace `ws` is re-aligned to 256 B
+    if it is not."""
+    flags = _lib.bwd_flags()                                 # the deterministic mode is read at backward time
+    nbytes = int(query(*args, flags))
+    if nbytes < 0:
+        _lib.check(nbytes, query.__name__)
+    bws = torch.empty(nbytes, dtype=torch.uint8, device=ws.device)
+    if ws.data_ptr() % 256:
+        ws = ws.clone()
+    with torch.cuda.device(ws.device):
+        rc = _lib.call_bwd(lambda f: call(ws, bws, f), flags, what)
+    _lib.check(rc, what)
+
+
+def _split_grads(gflat, shapes):
+    """The gradient of every parameter of `shapes` as a view of the flat gradient `gflat`."""
+    return [g.view(s) for g, s in zip(torch.split(gflat, [math.prod(s) for s in shapes]), shapes)]
+
+
+def _bridge_for(tensors, allowed=True):
+    """(the C++ fast path or None, `tensors` as it takes them).  train_model.py:561 runs the forward under autocast: the
+    custom ops' autocast rule (float inputs in fp32; the kernels are fp32 storage / fp32 accumulate there) is done here
+    by hand, so that the eager loop keeps the fast path."""
+    br = _eager_bridge() if allowed else None
+    if br is not None and torch.is_autocast_enabled("cuda"):
+        tensors = [t.float() if t.dtype in (torch.float16, torch.bfloat16) else t for t in tensors]
+    return br, tensors
+
+
+def _bridge_tables(edge_index, N, dev):
+    """(the CSR tables memoised on edge_index or [], the persistent counters the pass builds them in if there are none)"""
+    csr = _memo_tables(edge_index, N)
+    return csr, (None if csr else ops.csr_counters(dev, N))
+
+
+def _one_tensor(params):
+    """The custom ops' parameter list as ONE tensor (see lba_encoder)."""
+    return params[0] if len(params) == 1 else torch.cat([q.reshape(-1) for q in params])
 
 
 # ===================================================================================== protein encoder
@@ -233,28 +306,17 @@ def lba_forward(flat, x_s, x_v, ntypes, e_s, e_v, etypes, edge_index, csr, cfg, 
     nt = _i64(ntypes, "ntypes") if layout.nt_node > 0 else None
     et = _i64(etypes, "etypes") if layout.nt_edge > 0 else None
     ei = _i64(edge_index, "edge_index") if not csr else edge_index
-    masks = torch.empty(0, dtype=torch.float32, device=dev)
-    draw = False
-    if dropout_p > 0 and save_state:
-        if PINNED_MASKS is not None:
-            masks = PINNED_MASKS(2 * nc, N, MROW, dropout_p, dev)
-        else:
-            draw = True
+    masks, draw = _dropout(dropout_p, save_state, [(2 * nc, N, MROW)], dev)
+    masks = masks[0] if masks else torch.empty(0, dtype=torch.float32, device=dev)
     es = 2 if sdt == torch.bfloat16 else 4
     ws = alloc(lba_fwd_ws_bytes(N, E, nc, img, es, save_state), dtype=torch.uint8, device=dev)
     out = torch.empty(N, dims.out_s, dtype=sdt, device=dev)
-    batch = _lba_batch(x_s, x_v, nt, e_s, e_v, et, ei, csr, N, E)
-    with torch.cuda.device(dev):
-        counters = ops.csr_counters(dev, N) if not csr else None
-        rc = L.cgvp_lba_forward_pass(C.byref(dims), C.byref(layout), _ptr(flat), C.byref(batch), 1 if mean else 0,
-                                     float(dropout_p) if save_state else 0.0,
-                                     _ptr(rng_state("lba", dev)) if draw else None, _ptr(masks), _ptr(counters), _ptr(ws),
-                                     1 if save_state else 0, 0 if ops.FUSE_LAYER else 1, _ptr(out), _stream())
-    if rc != 0 and counters is not None:
-        counters.zero_()               # the persistent counters must not stay half-used (the next build assumes zeros)
-    _lib.check(rc, "cgvp_lba_forward_pass")
-    if draw:
-        _LAST_WS["lba"] = (ws, 0)
+    batch = _batch(_lib.LbaBatch, (x_s, x_v, nt), (e_s, e_v, et), ei, csr, N, E)
+    _forward_pass("lba", "cgvp_lba_forward_pass", lambda counters: L.cgvp_lba_forward_pass(
+        C.byref(dims), C.byref(layout), _ptr(flat), C.byref(batch), 1 if mean else 0,
+        float(dropout_p) if save_state else 0.0, _ptr(rng_state("lba", dev)) if draw else None, _ptr(masks),
+        _ptr(counters), _ptr(ws), 1 if save_state else 0, 0 if ops.FUSE_LAYER else 1, _ptr(out), _stream()),
+        ws, draw, csr, N)
     return out, ws, masks
 
 
@@ -311,11 +373,6 @@ def lba_backward(g_out, x_s, x_v, ntypes, e_s, e_v, etypes, edge_index, csr, ws,
     g_out = _f32(g_out.float(), "grad_output")               # every gradient buffer is fp32, whatever the storage type
     f32 = dict(dtype=torch.float32, device=dev)
     gparams = torch.empty(layout.total, **f32)               # every element is STORED by the pass's final reduce
-    flags = _lib.bwd_flags()                                 # the deterministic mode is read at backward time
-    nbytes = int(L.cgvp_lba_bwd_workspace_bytes_ex(C.byref(dims), C.byref(layout), N, E, flags))
-    if nbytes < 0:
-        _lib.check(nbytes, "cgvp_lba_bwd_workspace_bytes_ex")
-    bws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     g_x_s = torch.empty(N, dims.node_in_s, **f32) if need_x else None
     g_x_v = torch.empty(N, dims.node_in_v, 3, **f32) if need_x else None
     if need_e and int(e_s.shape[0]) != E:
@@ -323,15 +380,12 @@ def lba_backward(g_out, x_s, x_v, ntypes, e_s, e_v, etypes, edge_index, csr, ws,
     # rows of valid edges are STORED by the edge stage, the rest zero-filled by the pass (no edges: no edge stage)
     g_e_s = (torch.empty if E > 0 else torch.zeros)(E, dims.edge_in_s, **f32) if need_e else None
     g_e_v = (torch.empty if E > 0 else torch.zeros)(E, dims.edge_in_v, 3, **f32) if need_e else None
-    batch = _lba_batch(x_s, x_v, nt, e_s, e_v, et, edge_index, csr, N, E)
-    if ws.data_ptr() % 256:
-        ws = ws.clone()
-    with torch.cuda.device(dev):
-        rc = _lib.call_bwd(lambda f: L.cgvp_lba_backward_pass_ex(
+    batch = _batch(_lib.LbaBatch, (x_s, x_v, nt), (e_s, e_v, et), edge_index, csr, N, E)
+    _backward_pass(L.cgvp_lba_bwd_workspace_bytes_ex, (C.byref(dims), C.byref(layout), N, E),
+                   "cgvp_lba_backward_pass_ex", lambda ws, bws, f: L.cgvp_lba_backward_pass_ex(
             C.byref(dims), C.byref(layout), C.byref(batch), 1 if mean else 0, float(dropout_p), _ptr(masks), _ptr(ws),
             _ptr(g_out), _ptr(bws), _ptr(gparams), _ptr(g_x_s), _ptr(g_x_v), _ptr(g_e_s if E > 0 else None),
-            _ptr(g_e_v if E > 0 else None), f, _stream()), flags, "cgvp_lba_backward_pass_ex")
-    _lib.check(rc, "cgvp_lba_backward_pass_ex")
+            _ptr(g_e_v if E > 0 else None), f, _stream()), ws)
     none = lambda: torch.empty(0, **f32)                     # (outputs of a custom op must not alias each other)
     return (gparams, g_x_s if need_x else none(), g_x_v if need_x else none(), g_e_s if need_e else none(),
             g_e_v if need_e else none())
@@ -360,13 +414,6 @@ def _lba_setup(ctx, inputs, output):
     ctx.save_for_backward(x_s, x_v, ntypes, e_s, e_v, etypes, edge_index, ws, masks, *csr)
 
 
-def _numel(shape):
-    n = 1
-    for s in shape:
-        n *= s
-    return n
-
-
 def _lba_backward(ctx, g_out, g_ws, g_masks):
     if g_out is None:
         return (None,) * 8 + ([None] * ctx.ncsr, None, None, None)
@@ -376,7 +423,7 @@ def _lba_backward(ctx, g_out, g_ws, g_masks):
     gflat, g_x_s, g_x_v, g_e_s, g_e_v = torch.ops.caster_gvp.lba_encoder_backward(
         g_out.contiguous(), x_s, x_v, ntypes, e_s, e_v, etypes, edge_index, list(csr), ws, masks, ctx.cfg,
         ctx.dropout_p, need_x, need_e)
-    grads = [g.view(s) for g, s in zip(torch.split(gflat, [_numel(s) for s in ctx.shapes]), ctx.shapes)]
+    grads = _split_grads(gflat, ctx.shapes)
     if need_x and x_s.dtype != torch.float32:                 # input gradients are produced in fp32
         g_x_s, g_x_v = g_x_s.to(x_s.dtype), g_x_v.to(x_v.dtype)
     if need_e and e_s.dtype != torch.float32:
@@ -409,30 +456,20 @@ def lba_encoder(model, x_s, x_v, ntypes, e_s, e_v, etypes, edge_index, train_dro
            model.edge_hidden_channels[1], model.out_channels[0], model.num_ntypes, model.num_etypes,
            model.num_convs, 1 if model.aggr == "mean" else 0]
     p = float(model.dropout_rate) if train_dropout else 0.0
-    br = _eager_bridge()
-    if br is not None and torch.is_grad_enabled() and (e_s.requires_grad or e_v.requires_grad):
-        br = None       # gradients w.r.t. the raw edge features (rare: attribution studies): the custom-op path returns them
-    if br is not None and torch.is_autocast_enabled("cuda"):
-        # train_model.py:561 runs the forward under autocast: what the custom ops' autocast rule does (float inputs in fp32;
-        # the kernels are fp32 storage / fp32 accumulate there), done here so that the eager loop keeps the C++ fast path
-        x_s, x_v, e_s, e_v = (t.float() if t.dtype in (torch.float16, torch.bfloat16) else t for t in (x_s, x_v, e_s, e_v))
+    # gradients w.r.t. the raw edge features (rare: attribution studies): the custom-op path returns them
+    br, (x_s, x_v, e_s, e_v) = _bridge_for((x_s, x_v, e_s, e_v),
+                                           not (torch.is_grad_enabled() and (e_s.requires_grad or e_v.requires_grad)))
     if br is not None:
         # eager mode: the C++ autograd node (csrc/torch_bridge.cpp) -- same C entry points, a fraction of the host time
         dev, N = x_s.device, x_s.shape[0]
-        csr = _memo_tables(edge_index, N)
-        masks, draw = None, False
-        if p > 0 and save_state:
-            if PINNED_MASKS is not None:
-                masks = PINNED_MASKS(2 * model.num_convs, N, MROW, p, dev)
-            else:
-                draw = True
+        csr, counters = _bridge_tables(edge_index, N, dev)
+        masks, draw = _dropout(p, save_state, [(2 * model.num_convs, N, MROW)], dev)
         params = model.op_params()
         with torch.cuda.device(dev):
             out, ws, zero_copy = br.lba_encoder(params, x_s, x_v, ntypes, e_s, e_v, etypes, edge_index, csr, cfg, p,
-                                                save_state, masks, rng_state("lba", dev) if draw else None,
-                                                None if csr else ops.csr_counters(dev, N), ops.FUSE_LAYER)
-        if draw:
-            _LAST_WS["lba"] = (ws, 0)
+                                                save_state, masks[0] if masks else None,
+                                                rng_state("lba", dev) if draw else None, counters, ops.FUSE_LAYER)
+        _record_draw("lba", ws, draw)
         if not zero_copy and not model._fused and model._onehot_ntypes and model._onehot_etypes:
             model._arena.rebuild()          # something re-materialised the parameters: re-seat them as arena views
         return out
@@ -440,10 +477,9 @@ def lba_encoder(model, x_s, x_v, ntypes, e_s, e_v, etypes, edge_index, train_dro
     # list costs ~0.3 ms of torch.library marshalling per call (forward, and again for the split gradients), measured on
     # the CPU.  `cat` keeps autograd's connection to the leaves: under torch.compile Inductor emits one small copy kernel
     # and the backward's split is 50 views; in eager mode it is one extra launch.
-    params = model.op_params()
-    arena = params[0] if len(params) == 1 else torch.cat([q.reshape(-1) for q in params])
     out, _, _ = torch.ops.caster_gvp.lba_encoder(
-        [arena], x_s, x_v, ntypes, e_s, e_v, etypes, edge_index, _memo_tables(edge_index, x_s.shape[0]), cfg,
+        [_one_tensor(model.op_params())], x_s, x_v, ntypes, e_s, e_v, etypes, edge_index,
+        _memo_tables(edge_index, x_s.shape[0]), cfg,
         p, save_state)
     return out
 
@@ -495,13 +531,6 @@ def _gine_weights(params, nl):
     return arr, keep
 
 
-def _gine_batch(x, nt, eattr, et, edge_index, csr, N, E):
-    rp, ep, es_, ed = _csr_ptrs(csr)
-    return _lib.GineBatch(N, E, x.data_ptr(), nt.data_ptr() if nt is not None else 0, eattr.data_ptr() if E > 0 else 0,
-                          et.data_ptr() if (et is not None and E > 0) else 0,
-                          edge_index.data_ptr() if (E > 0 and not csr) else 0, rp, ep, es_, ed)
-
-
 def _mask_ptrs(masks, nl):
     live = [m for m in masks if m.numel()]
     if not live:
@@ -541,28 +570,15 @@ def gine_forward(params, x, ntypes, eattr, etypes, edge_index, csr, widths, num_
     nt = _i64(ntypes, "ntypes") if num_ntypes > 0 else None
     et = _i64(etypes, "etypes") if num_etypes > 0 else None
     ei = _i64(edge_index, "edge_index") if not csr else edge_index
-    masks, draw = [], False
-    if dropout_p > 0 and nl > 1 and save_state:
-        if PINNED_MASKS is not None:
-            masks = [PINNED_MASKS(1, N, widths[l + 1], dropout_p, dev)[0].contiguous() for l in range(nl - 1)]
-        else:
-            draw = True
-    if not masks:
-        masks = [x.new_empty(0) for _ in range(nl - 1)]
+    masks, draw = _dropout(dropout_p, save_state, [(1, N, widths[l + 1]) for l in range(nl - 1)], dev)
+    masks = [m[0].contiguous() for m in masks] if masks else [x.new_empty(0) for _ in range(nl - 1)]
     ws = alloc(gine_fwd_ws_bytes(N, E, widths, save_state), dtype=torch.uint8, device=dev)
     out = torch.empty(N, widths[-1], dtype=torch.float32, device=dev)
-    batch = _gine_batch(x, nt, eattr, et, ei, csr, N, E)
-    with torch.cuda.device(dev):
-        counters = ops.csr_counters(dev, N) if not csr else None
-        rc = L.cgvp_gine_forward_pass(C.byref(cfg), warr, C.byref(batch), float(dropout_p) if save_state else 0.0,
-                                      _ptr(rng_state("gine", dev)) if draw else None, _mask_ptrs(masks, nl), _ptr(counters),
-                                      _ptr(ws), 1 if save_state else 0, 0 if ops.VARIANT == "mfma" else 1, _ptr(out),
-                                      _stream())
-    if rc != 0 and counters is not None:
-        counters.zero_()
-    _lib.check(rc, "cgvp_gine_forward_pass")
-    if draw:
-        _LAST_WS["gine"] = (ws, 0)
+    batch = _batch(_lib.GineBatch, (x, nt), (eattr, et), ei, csr, N, E)
+    _forward_pass("gine", "cgvp_gine_forward_pass", lambda counters: L.cgvp_gine_forward_pass(
+        C.byref(cfg), warr, C.byref(batch), float(dropout_p) if save_state else 0.0,
+        _ptr(rng_state("gine", dev)) if draw else None, _mask_ptrs(masks, nl), _ptr(counters), _ptr(ws),
+        1 if save_state else 0, 0 if ops.VARIANT == "mfma" else 1, _ptr(out), _stream()), ws, draw, csr, N)
     return out, ws, masks
 
 
@@ -604,20 +620,12 @@ def gine_backward(g_out, params, x, ntypes, eattr, etypes, edge_index, csr, ws, 
     et = _i64(etypes, "etypes") if num_etypes > 0 else None
     g = _f32(g_out, "grad_output")
     gflat = torch.empty(sum(p.numel() for p in params), **f32)        # every element is STORED by the pass's reduce
-    flags = _lib.bwd_flags()                                 # the deterministic mode is read at backward time
-    nbytes = int(L.cgvp_gine_bwd_workspace_bytes_ex(C.byref(cfg), N, E, flags))
-    if nbytes < 0:
-        _lib.check(nbytes, "cgvp_gine_bwd_workspace_bytes_ex")
-    bws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     g_x = torch.empty(N, widths[0] - num_ntypes, **f32) if need_x else None
-    batch = _gine_batch(x, nt, eattr, et, edge_index, csr, N, E)
-    if ws.data_ptr() % 256:
-        ws = ws.clone()
-    with torch.cuda.device(dev):
-        rc = _lib.call_bwd(lambda f: L.cgvp_gine_backward_pass_ex(
+    batch = _batch(_lib.GineBatch, (x, nt), (eattr, et), edge_index, csr, N, E)
+    _backward_pass(L.cgvp_gine_bwd_workspace_bytes_ex, (C.byref(cfg), N, E),
+                   "cgvp_gine_backward_pass_ex", lambda ws, bws, f: L.cgvp_gine_backward_pass_ex(
             C.byref(cfg), warr, C.byref(batch), float(dropout_p), _mask_ptrs(masks, nl), _ptr(ws), _ptr(g), _ptr(bws),
-            _ptr(gflat), _ptr(g_x), int(bwd_workgroups), f, _stream()), flags, "cgvp_gine_backward_pass_ex")
-    _lib.check(rc, "cgvp_gine_backward_pass_ex")
+            _ptr(gflat), _ptr(g_x), int(bwd_workgroups), f, _stream()), ws)
     return gflat, (g_x if need_x else torch.empty(0, **f32))
 
 
@@ -650,8 +658,8 @@ def _gine_backward(ctx, g_out, g_ws, g_masks):
     gflat, g_x = torch.ops.caster_gvp.gine_encoder_backward(
         g_out.contiguous(), params, x, ntypes, eattr, etypes, edge_index, list(csr), ws, list(masks), widths, num_ntypes,
         num_etypes, slope, dropout_p, need_x, GINE_BWD_WORKGROUPS)
-    grads = [g.view(s) for g, s in zip(torch.split(gflat, [_numel(s) for s in ctx.shapes]), ctx.shapes)]
-    return (grads, g_x if need_x else None, None, None, None, None, [None] * n_csr, None, None, None, None, None, None)
+    return (_split_grads(gflat, ctx.shapes), g_x if need_x else None, None, None, None, None, [None] * n_csr, None, None,
+            None, None, None, None)
 
 
 # Cap on the CUs of the GINE backward (0 = the library default of 16: inside JointGNN it runs beside the
@@ -683,33 +691,24 @@ def gine_encoder(model, x, ntypes, eattr, etypes, edge_index, slope, train_dropo
     if eattr.requires_grad:
         raise NotImplementedError("gradients w.r.t. bond features are not produced by the backward kernels")
     p = float(model.dropout_rate) if train_dropout else 0.0
-    br = _eager_bridge()
-    if br is not None and torch.is_autocast_enabled("cuda"):           # (as in lba_encoder: the ops' autocast rule, by hand)
-        x, eattr = (t.float() if t.dtype in (torch.float16, torch.bfloat16) else t for t in (x, eattr))
+    br, (x, eattr) = _bridge_for((x, eattr))
     if br is not None:
         dev, N = x.device, x.shape[0]
-        csr = _memo_tables(edge_index, N)
+        csr, counters = _bridge_tables(edge_index, N, dev)
         widths = list(model._widths)
-        masks, draw = [], False
-        if p > 0 and save_state and len(widths) > 2:
-            if PINNED_MASKS is not None:
-                masks = [PINNED_MASKS(1, N, widths[l + 1], p, dev)[0].contiguous() for l in range(len(widths) - 2)]
-            else:
-                draw = True
+        masks, draw = _dropout(p, save_state, [(1, N, w) for w in widths[1:-1]], dev)
         params = gine_params(model, one_leaf_ok=True)
         with torch.cuda.device(dev):
             out, ws = br.gine_encoder(params, x, ntypes, eattr, etypes, edge_index, csr, widths,
                                       model.num_ntypes if model._onehot_ntypes else 0,
-                                      model.num_etypes, float(slope), p, save_state, masks,
-                                      rng_state("gine", dev) if draw else None, None if csr else ops.csr_counters(dev, N),
-                                      0, GINE_BWD_WORKGROUPS)
-        if draw:
-            _LAST_WS["gine"] = (ws, 0)
+                                      model.num_etypes, float(slope), p, save_state,
+                                      [m[0].contiguous() for m in masks] if masks else [],
+                                      rng_state("gine", dev) if draw else None, counters, 0, GINE_BWD_WORKGROUPS)
+        _record_draw("gine", ws, draw)
         return out
     # custom-op path (torch.compile; CGVP_BRIDGE=0): the kernel weights as ONE tensor (see lba_encoder)
-    params = gine_params(model)
-    flat = params[0] if len(params) == 1 else torch.cat([q.reshape(-1) for q in params])
     out, _, _ = torch.ops.caster_gvp.gine_encoder(
-        [flat], x, ntypes, eattr, etypes, edge_index, _memo_tables(edge_index, x.shape[0]), list(model._widths),
+        [_one_tensor(gine_params(model))], x, ntypes, eattr, etypes, edge_index, _memo_tables(edge_index, x.shape[0]),
+        list(model._widths),
         model.num_ntypes if model._onehot_ntypes else 0, model.num_etypes, float(slope), p, save_state)
     return out

@@ -29,26 +29,21 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else C.c_void_p(0)
 
 
-def _f32(t, name):
+def _on_gpu(t, name, note="; there is no CPU path"):
     if not t.is_cuda:
-        raise RuntimeError(f"{name}: caster-dta_amd runs on MI355X only (got a {t.device} tensor); "
-                           "there is no CPU path")
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name}: expected float32, got {t.dtype}")
-    t = t.contiguous()
-    if t.data_ptr() % 16:
-        t = t.clone()
-    return t
+        raise RuntimeError(f"{name}: caster-dta_amd runs on MI355X only (got a {t.device} tensor){note}")
 
 
-def _act(t, name, dtype):
+def _f32(t, name):
+    return _act(t, name, torch.float32, accepted=(torch.float32,))
+
+
+def _act(t, name, dtype, accepted=(torch.float32, torch.bfloat16)):
     """An ACTIVATION buffer (features, node rows, edge-embedding store): contiguous, 16-B aligned, of the pass's
     storage dtype (torch.float32 or torch.bfloat16 -- cast here if the caller mixed them)."""
-    if not t.is_cuda:
-        raise RuntimeError(f"{name}: caster-dta_amd runs on MI355X only (got a {t.device} tensor); "
-                           "there is no CPU path")
-    if t.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError(f"{name}: expected float32 or bfloat16, got {t.dtype}")
+    _on_gpu(t, name)
+    if t.dtype not in accepted:
+        raise TypeError(f"{name}: expected {' or '.join(str(d)[len('torch.'):] for d in accepted)}, got {t.dtype}")
     if t.dtype != dtype:
         t = t.to(dtype)
     t = t.contiguous()
@@ -63,8 +58,7 @@ def storage_dtype(*tensors):
 
 
 def _i64(t, name):
-    if not t.is_cuda:
-        raise RuntimeError(f"{name}: caster-dta_amd runs on MI355X only (got a {t.device} tensor)")
+    _on_gpu(t, name, note="")
     if t.dtype != torch.int64:
         t = t.long()
     return t.contiguous()
