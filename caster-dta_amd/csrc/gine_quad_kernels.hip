@@ -12,6 +12,7 @@
 //                transposed on the matrix cores), biases by DPP row sums
 //   C. edges   : dm = relu'(m) dh[target]  -> float atomics into g_x[source];
 //                dW_e = dm (x) [onehot | features], db_e, d eps
+//                (EG instantiations: d eattr[eid] (+)= the feature columns of W_e^T dm, one more transposed chain)
 // Weight-gradient partials go to a wave-private block in LDS (AccPriv, state_dict order of the
 // layer); the workgroup sums its four blocks and writes ONE slab row.  Fragments are built from
 // the plain nn.Linear weights while staging them into LDS (the matrices are tiny), so GINE needs
@@ -97,6 +98,11 @@ struct GineQArgs {
   // STORE instantiation (deterministic mode, selected by g_edge != NULL): d x[src] of every sorted edge -> g_edge [E][XW],
   // (1+eps) dh -> g_self [N][XW] (neither when g_self is NULL); quad::src_sum adds them up in a fixed order (g_x unused)
   float* g_edge; float* g_self;
+  // EG instantiations (selected by g_eattr != NULL): d eattr [E][ED], rows at the ORIGINAL edge ids.  Every layer has its own
+  // `lin` over the same bond features, so the layers' launches add up: the first one of a pass stores its rows
+  // (eattr_accum = 0, no zero fill), the later ones read-add-write them.  An edge belongs to one lane group of one wave
+  // per launch, and the launches of a pass are ordered on one stream: plain loads and stores, no atomics.
+  float* g_eattr; int eattr_accum;
 };
 
 // dropout factors of channels 16 mt + 4 g .. + 3 of atom n (given mask row of width COUT, or regenerated)
@@ -111,7 +117,7 @@ __device__ __forceinline__ f4 gine_dropout(const float* mask, const gvp::RngArgs
   return f4{1.f, 1.f, 1.f, 1.f};
 }
 
-template <int CIN, int CHID, int COUT, int NT, int NET, int ED>
+template <int CIN, int CHID, int COUT, int NT, int NET, int ED, bool EG = false>
 struct GineQ {
   static_assert(CHID % 16 == 0 && COUT % 16 == 0 && COUT <= 64, "hidden / output widths are whole 16-channel tiles (<= 4 output tiles)");
   static constexpr int KE = NET + ED, XW = CIN - NT, CINP = (CIN + 15) / 16 * 16;
@@ -129,11 +135,15 @@ struct GineQ {
   typedef Gemm<P1, COUT, CHID, KHid> G1;        // lins.1   [COUT][CHID]
   typedef GemmT<KHid, KOut, CHID> G1T;
   typedef GemmT<KIn, KHid, CIN> G0T;
+  typedef GemmT<KFeat, KIn, KE> GET;            // d [onehot | features] = W_e^T dm (EG only): K = CINP, one 16-slot tile
+  static_assert(GET::MT == 1, "d eattr is one output tile");
   static constexpr int F_E = 0, F_0 = F_E + GE::NFRAG * 64, F_0T = F_0 + G0::NFRAG * 64, F_1 = F_0T + G0T::NFRAG * 64,
                        F_1T = F_1 + G1::NFRAG * 64,
                        // the three bias vectors sit behind the fragments (be zero-padded to CINP): the tile loops read
                        // them from LDS -- a global load per use put a memory round trip in front of every GEMM
-                       V_BE = F_1T + G1T::NFRAG * 64, V_B0 = V_BE + CINP, V_B1 = V_B0 + CHID, F_SIZE = V_B1 + COUT;
+                       V_BE = F_1T + G1T::NFRAG * 64, V_B0 = V_BE + CINP, V_B1 = V_B0 + CHID,
+                       // EG: the transposed lin fragments behind everything the other instantiations stage
+                       F_ET = V_B1 + COUT, F_SIZE = F_ET + (EG ? GET::NFRAG * 64 : 0);
   static constexpr int ROWS = TILE * CINP;       // per wave: agg rows, then dh rows
   // Waves per workgroup: as many as one CU's LDS holds (the grid is capped at the 16 CUs the protein
   // backward leaves free, so waves per CU is what sets the number of tiles a wave has to walk).
@@ -325,9 +335,12 @@ __device__ __forceinline__ void dw1_band(const f4 (&AT)[Q::MO], const f4 (&BT)[Q
 // (cgvp_gine_fwd_ws.agg / .pos): phase A -- the gather of the source rows (CIN floats per edge), W_e e, ReLU and the segmented
 // sum, 48 % of a tile's cycles in the round-3 stamps -- is replaced by one row load per atom, and the edge phase reads 8 bytes
 // of pattern per edge instead of recomputing the messages.  !SAVED: the fine-grained entry point (no forward workspace).
-template <int CIN, int CHID, int COUT, int NT, int NET, int ED, bool SAVED, bool STORE = false>
-__global__ __launch_bounds__((WAVE * GineQ<CIN, CHID, COUT, NT, NET, ED>::WPB)) void gine_quad_bwd_kernel(GineQArgs a) {
-  typedef GineQ<CIN, CHID, COUT, NT, NET, ED> Q;
+// EG: also return the gradient of the bond features (GineQArgs::g_eattr); its own instantiations, so a pass that does not
+// ask for it launches the kernels it always did.
+template <int CIN, int CHID, int COUT, int NT, int NET, int ED, bool SAVED, bool STORE = false, bool EG = false>
+__global__ __launch_bounds__((WAVE * GineQ<CIN, CHID, COUT, NT, NET, ED, EG>::WPB)) void gine_quad_bwd_kernel(GineQArgs a) {
+  typedef GineQ<CIN, CHID, COUT, NT, NET, ED, EG> Q;
+  static_assert(Q::WPB == GineQ<CIN, CHID, COUT, NT, NET, ED>::WPB, "the extra fragment group must not cost a wave");
   constexpr int GQ_WPB = Q::WPB, GQ_TPB = Q::TPB;
   constexpr int KE = Q::KE, XW = Q::XW, CINP = Q::CINP, MI = Q::MI, MH = Q::MH, MO = Q::MO;
   extern __shared__ __attribute__((aligned(16))) float lds[];       // lds[0..GQ_TPB): AccPriv::trash()
@@ -342,6 +355,7 @@ __global__ __launch_bounds__((WAVE * GineQ<CIN, CHID, COUT, NT, NET, ED>::WPB)) 
   stage_fragments<typename Q::G0T, GQ_TPB>(frag + Q::F_0T, a.w0);
   stage_fragments<typename Q::G1, GQ_TPB>(frag + Q::F_1, a.w1);
   stage_fragments<typename Q::G1T, GQ_TPB>(frag + Q::F_1T, a.w1);
+  if constexpr (EG) stage_fragments<typename Q::GET, GQ_TPB>(frag + Q::F_ET, a.we);
   stage_biases<CIN, CINP, CHID, COUT, GQ_TPB>(frag + Q::V_BE, frag + Q::V_B0, frag + Q::V_B1, a.be, a.b0, a.b1);
   for (int k = lane0; k < Q::BLK / 4; k += WAVE) reinterpret_cast<f4*>(blk)[k] = f4{0.f, 0.f, 0.f, 0.f};
   GSTAMP(0);
@@ -365,6 +379,7 @@ __global__ __launch_bounds__((WAVE * GineQ<CIN, CHID, COUT, NT, NET, ED>::WPB)) 
     // a chunk costs ~4 dependent memory hops instead of 3 per edge tile.  Molecules have <= 64 incoming
     // edges per 16 atoms almost always; then phase C reuses the registers and issues no loads at all.
     int32_t c_src[NTL], c_dst[NTL];
+    [[maybe_unused]] int32_t c_eid[NTL];                   // EG: original edge ids, the rows of g_eattr
     float c_fs[NTL][1][4];
     unsigned c_pos[NTL];                                   // bit 4 mt + r: message channel passed the ReLU
     const bool single = !SAVED && e1 - e0 <= NTL * TILE;
@@ -379,6 +394,7 @@ __global__ __launch_bounds__((WAVE * GineQ<CIN, CHID, COUT, NT, NET, ED>::WPB)) 
         const int32_t eid = __shfl(m_eid, sl), et = __shfl(m_et, sl);
         c_src[t] = __shfl(m_src, sl);
         c_dst[t] = __shfl(m_dst, sl);                      // -1: no such edge
+        if constexpr (EG) c_eid[t] = eid;
         edge_inputs<Q, CIN, NT, NET, ED, G_PIN>(a, eid, et, c_src[t], c_dst[t] >= 0, g, c_fs[t][0], xj[t]);
       }
     };
@@ -581,6 +597,7 @@ __global__ __launch_bounds__((WAVE * GineQ<CIN, CHID, COUT, NT, NET, ED>::WPB)) 
           const int32_t eid = __shfl(m_eid, sl), et = __shfl(m_et, sl);
           c_src[t] = __shfl(m_src, sl);
           c_dst[t] = __shfl(m_dst, sl);
+          if constexpr (EG) c_eid[t] = eid;
           edge_features<Q, NET, ED>(a, eid, et, c_dst[t] >= 0, g, c_fs[t][0]);
           const int32_t p = c0 + sl;
           const unsigned bits = a.pos_in[(int64_t)(p < e1 ? p : e1 - 1) * 4 + g];
@@ -618,6 +635,27 @@ __global__ __launch_bounds__((WAVE * GineQ<CIN, CHID, COUT, NT, NET, ED>::WPB)) 
               if (a.g_x && c >= NT && c < CIN && dm[mt][r] != 0.f)
                 atomicAdd(a.g_x + (int64_t)src * XW + (c - NT), dm[mt][r]);
             }
+          }
+        }
+        if constexpr (EG) {
+          // d [onehot | features] = W_e^T dm: the lane's dm slots are the B operand as they stand; register r of the
+          // tile is k-slot r of the edge (column 4 r + g).  Only the ED feature columns have a gradient to return.
+          float bdm[1][Q::KIn::steps];
+#pragma unroll
+          for (int s = 0; s < Q::KIn::steps; ++s) bdm[0][s] = dms[s];
+          f4 de[1] = {zero};
+          apply<typename Q::GET, 1>(frag + Q::F_ET, 0, bdm, de, lane);
+          float* const row = a.g_eattr + (int64_t)(active ? c_eid[t] : 0) * ED;
+          float old[4];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int k = 4 * r + g - NET;
+            old[r] = (a.eattr_accum && active && k >= 0 && k < ED) ? row[k] : 0.f;
+          }
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int k = 4 * r + g - NET;
+            if (active && k >= 0 && k < ED) row[k] = old[r] + de[0][r];
           }
         }
         f4 AT[MI], BT[1], acc[MI][1];
@@ -816,6 +854,25 @@ int launch(GineQArgs& a, int cap, int* rows, int* row_len, hipStream_t st) {
   const int64_t tiles = (a.N + TILE - 1) / TILE;
   int64_t wgs = (tiles + GQ_WPB - 1) / GQ_WPB;
   const int G = (int)(wgs < 1 ? 1 : (wgs > cap ? cap : wgs));
+  if (a.g_eattr) {             // the same three forms with the bond-feature gradient: same grid, one more fragment group in LDS
+    typedef GineQ<CIN, CHID, COUT, NT, NET, ED, true> QE;
+    static_assert(QE::TPB == Q::TPB && QE::L_SIZE == Q::L_SIZE, "same workgroup shape and slab row");
+    const size_t ldse = (size_t)QE::LDS_FLOATS * sizeof(float);
+    if (a.g_edge) {
+      if (!(a.agg_in && a.pos_in)) return CGVP_ERR_NONDETERMINISTIC;
+      CGVP_SET_DYN_LDS_ONCE((gine_quad_bwd_kernel<CIN, CHID, COUT, NT, NET, ED, true, true, true>), ldse);
+      hipLaunchKernelGGL((gine_quad_bwd_kernel<CIN, CHID, COUT, NT, NET, ED, true, true, true>), dim3(G), dim3(GQ_TPB), ldse, st, a);
+    } else if (a.agg_in && a.pos_in) {
+      CGVP_SET_DYN_LDS_ONCE((gine_quad_bwd_kernel<CIN, CHID, COUT, NT, NET, ED, true, false, true>), ldse);
+      hipLaunchKernelGGL((gine_quad_bwd_kernel<CIN, CHID, COUT, NT, NET, ED, true, false, true>), dim3(G), dim3(GQ_TPB), ldse, st, a);
+    } else {
+      CGVP_SET_DYN_LDS_ONCE((gine_quad_bwd_kernel<CIN, CHID, COUT, NT, NET, ED, false, false, true>), ldse);
+      hipLaunchKernelGGL((gine_quad_bwd_kernel<CIN, CHID, COUT, NT, NET, ED, false, false, true>), dim3(G), dim3(GQ_TPB), ldse, st, a);
+    }
+    *rows = G;
+    *row_len = Q::L_SIZE;
+    return 0;
+  }
   const size_t lds = (size_t)Q::LDS_FLOATS * sizeof(float);
   if (a.g_edge) {              // deterministic mode: the SAVED path only
     if (!(a.agg_in && a.pos_in)) return CGVP_ERR_NONDETERMINISTIC;
@@ -842,11 +899,11 @@ int gine_bwd(int cin, int chid, int cout, int nt, int net, int ed, const float* 
              const int32_t* esrc, const int32_t* edst, int64_t N, const cgvp_gine_w* w, float slope,
              const float* mask, gvp::RngArgs rng, const float* g_out, float* g_x, float* slab, int max_workgroups,
              int* rows, int* row_len, hipStream_t st, const float* agg_in, const uint16_t* pos_in,
-             float* g_edge, float* g_self) {
+             float* g_edge, float* g_self, float* g_eattr, int eattr_accum) {
   const int cap = max_workgroups <= 0 ? kGineBwdDefaultGrid : (max_workgroups > kGineBwdMaxGrid ? kGineBwdMaxGrid : max_workgroups);
   if (((uintptr_t)agg_in & 15) || ((uintptr_t)pos_in & 1)) return CGVP_ERR_BAD_ARG;
   GineQArgs a{x, ntypes, eattr, etypes, rowptr, eperm, esrc, edst, N, w->eps, w->we, w->be, w->w0, w->b0,
-              w->w1, w->b1, slope, mask, rng, g_out, g_x, slab, agg_in, pos_in, g_edge, g_self};
+              w->w1, w->b1, slope, mask, rng, g_out, g_x, slab, agg_in, pos_in, g_edge, g_self, g_eattr, eattr_accum};
   // compiled for the layer shapes of HomoMoleculeGNN_GINE in CASTER-DTA (molecule_gnn.py:240-250)
   if (cin == 52 && chid == 16 && cout == 16 && nt == 11 && net == 5 && ed == 9) return launch<52, 16, 16, 11, 5, 9>(a, cap, rows, row_len, st);
   if (cin == 52 && chid == 16 && cout == 16 && nt == 0 && net == 5 && ed == 9) return launch<52, 16, 16, 0, 5, 9>(a, cap, rows, row_len, st);   // nn.Embedding atom types (11-wide), materialised by the host

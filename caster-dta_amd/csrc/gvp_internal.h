@@ -111,7 +111,9 @@ int gine_bwd(int cin, int chid, int cout, int nt, int net, int ed, const float* 
              const int32_t* esrc, const int32_t* edst, int64_t N, const cgvp_gine_w* w, float slope,
              const float* mask, gvp::RngArgs rng, const float* g_out, float* g_x, float* slab, int max_workgroups, int* rows,
              int* row_len, hipStream_t st, const float* agg_in = nullptr, const uint16_t* pos_in = nullptr,
-             float* g_edge = nullptr, float* g_self = nullptr);
+             float* g_edge = nullptr, float* g_self = nullptr,
+             // d eattr [E][ed] at the original edge ids, or NULL; eattr_accum: 0 = store the rows, 1 = add to them
+             float* g_eattr = nullptr, int eattr_accum = 0);
 int gine_fwd(int cin, int chid, int cout, int nt, int net, int ed, const float* x, const int64_t* ntypes,
              const float* eattr, const int64_t* etypes, const int32_t* rowptr, const int32_t* eperm,
              const int32_t* esrc, const int32_t* edst, int64_t N, const cgvp_gine_w* w, float slope,

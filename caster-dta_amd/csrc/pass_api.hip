@@ -554,13 +554,21 @@ int cgvp_gine_backward_pass(const cgvp_gine_cfg* cfg, const cgvp_gine_w* w, cons
                             const float* const* masks, const void* fwd_workspace, const float* g_out, void* bwd_workspace,
                             float* grad_flat, float* g_x, int32_t max_workgroups, void* stream) {
   if (quad::deterministic_env()) return CGVP_ERR_NONDETERMINISTIC;     // its workspace has no room for the stored rows
-  return cgvp_gine_backward_pass_ex(cfg, w, batch, dropout_p, masks, fwd_workspace, g_out, bwd_workspace, grad_flat, g_x,
-                                    max_workgroups, 0, stream);
+  return cgvp_gine_backward_pass_eattr(cfg, w, batch, dropout_p, masks, fwd_workspace, g_out, bwd_workspace, grad_flat, g_x,
+                                       nullptr, max_workgroups, 0, stream);
 }
 
 int cgvp_gine_backward_pass_ex(const cgvp_gine_cfg* cfg, const cgvp_gine_w* w, const cgvp_gine_batch* batch, float dropout_p,
                                const float* const* masks, const void* fwd_workspace, const float* g_out, void* bwd_workspace,
                                float* grad_flat, float* g_x, int32_t max_workgroups, int32_t flags, void* stream) {
+  return cgvp_gine_backward_pass_eattr(cfg, w, batch, dropout_p, masks, fwd_workspace, g_out, bwd_workspace, grad_flat, g_x,
+                                       nullptr, max_workgroups, flags, stream);
+}
+
+int cgvp_gine_backward_pass_eattr(const cgvp_gine_cfg* cfg, const cgvp_gine_w* w, const cgvp_gine_batch* batch, float dropout_p,
+                                  const float* const* masks, const void* fwd_workspace, const float* g_out, void* bwd_workspace,
+                                  float* grad_flat, float* g_x, float* g_eattr, int32_t max_workgroups, int32_t flags,
+                                  void* stream) {
   const bool det = det_mode(flags);
   if (det && gine_recompute()) return CGVP_ERR_NONDETERMINISTIC;     // the recomputing kernel has no STORE instantiation
   if (!cfg || !w || !batch || !fwd_workspace || !bwd_workspace || !grad_flat) return CGVP_ERR_BAD_ARG;
@@ -621,7 +629,8 @@ int cgvp_gine_backward_pass_ex(const cgvp_gine_cfg* cfg, const cgvp_gine_w* w, c
                                 &rows, &row_len, st, gine_recompute() ? nullptr : at<float>(fwd_workspace, ws.agg[l]),
                                 gine_recompute() ? nullptr : at<uint16_t>(fwd_workspace, ws.pos[l]),
                                 det ? at<float>(bwd_workspace, dw.rows) : nullptr,          // (the STORE kernel even
-                                (det && gxl) ? at<float>(bwd_workspace, dw.extra) : nullptr))  //  when no d x is wanted)
+                                (det && gxl) ? at<float>(bwd_workspace, dw.extra) : nullptr,   //  when no d x is wanted)
+                                g_eattr, l < L - 1))      // d eattr: the launch that runs first stores, the others add
       return rc;
     if (det && gxl)
       if (int rc = quad::src_sum(cfg->widths[l] - (first ? cfg->num_ntypes : 0), at<float>(bwd_workspace, dw.rows),

@@ -517,17 +517,22 @@ void gine_weights(const std::vector<at::Tensor>& params, int L, std::vector<at::
 
 struct GineBackward : public EncoderBackward<GineBackward> {
   static constexpr PassNames kNames{"CasterGvpGineEncoderBackward", "drug", "gine_bwd.apply", "gine_bwd.c_call",
-                                    "gine_bwd.views", "cgvp_gine_bwd_workspace_bytes_ex", "cgvp_gine_backward_pass_ex"};
-  using InputGrads = std::array<at::Tensor, 1>;     // g_x
+                                    "gine_bwd.views", "cgvp_gine_bwd_workspace_bytes_ex", "cgvp_gine_backward_pass_eattr"};
+  using InputGrads = std::array<at::Tensor, 2>;     // g_x, g_eattr
 
   GineMeta meta;
   std::vector<at::Tensor> params, masks;    // the 7 L kernel tensors (views of the arena in one-leaf mode)
   at::Tensor x, ntypes, eattr, etypes;
   int max_workgroups = 0;
+  bool need_gx = false, need_geattr = false;    // which of the two inputs required a gradient at the forward
 
   int64_t workspace_bytes(int32_t flags) const { return cgvp_gine_bwd_workspace_bytes_ex(&meta.cfg, N, E, flags); }
+  // an input that did not ask stays undefined: NULL to the pass, which then launches what it launches without it
   InputGrads input_grads(const at::TensorOptions& f32) const {
-    return {at::empty({N, (int64_t)(meta.cfg.widths[0] - meta.cfg.num_ntypes)}, f32)};
+    InputGrads g;
+    if (need_gx) g[0] = at::empty({N, (int64_t)(meta.cfg.widths[0] - meta.cfg.num_ntypes)}, f32);
+    if (need_geattr) g[1] = at::empty({E, (int64_t)meta.cfg.edge_dim}, f32);      // every row STORED by the pass
+    return g;
   }
   at::Tensor input_grad(const at::Tensor& g) const { return g; }
   auto backward_call(const at::Tensor& g_out, const at::Tensor& bws, const at::Tensor& garena, const InputGrads& g_in) {
@@ -540,9 +545,9 @@ struct GineBackward : public EncoderBackward<GineBackward> {
     for (const at::Tensor& m : masks) mp.push_back((const float*)ptr(m));
     // (`keep` holds the weights the pointers in `w` point into)
     return [this, keep = std::move(keep), w = std::move(w), mp = std::move(mp), b, &g_out, &bws, &garena, &g_in](int32_t f) {
-      return cgvp_gine_backward_pass_ex(&meta.cfg, w.data(), &b, (float)dropout_p, mp.empty() ? nullptr : mp.data(),
-                                        ptr(ws), (const float*)ptr(g_out), ptr(bws), (float*)ptr(garena),
-                                        (float*)ptr(g_in[0]), max_workgroups, f, current_stream(x));
+      return cgvp_gine_backward_pass_eattr(&meta.cfg, w.data(), &b, (float)dropout_p, mp.empty() ? nullptr : mp.data(),
+                                           ptr(ws), (const float*)ptr(g_out), ptr(bws), (float*)ptr(garena),
+                                           (float*)ptr(g_in[0]), (float*)ptr(g_in[1]), max_workgroups, f, current_stream(x));
     };
   }
   void release_inputs() { x.reset(); eattr.reset(); ntypes.reset(); etypes.reset(); params.clear(); masks.clear(); }
@@ -593,8 +598,10 @@ std::tuple<at::Tensor, at::Tensor> gine_encoder(std::vector<at::Tensor> params_i
   check_forward(rc, counters, "cgvp_gine_forward_pass");
   if (!save_state) return {out, at::Tensor()};
   if (GineBackward* node = attach_node<GineBackward>(out, params_in, one_leaf, {ws, std::move(csr), N, E, d.p},
-                                                     {{x, "x"}, {eattr, "eattr"}}, x_in)) {
+                                                     {{x, "x"}, {eattr, "eattr"}}, x_in, eattr_in)) {
     node->meta = meta;
+    node->need_gx = x_in.requires_grad();
+    node->need_geattr = eattr_in.requires_grad();
     node->params.reserve(params.size());
     for (const at::Tensor& p : params) {
       node->params.push_back(p.detach());

@@ -15,11 +15,11 @@ import torch  # noqa: F401  (must be imported first: its libamdhip64.so.7 is the
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # CGVP_LIB_PATH: A/B builds of the same ABI (diagnostics); the default is the in-tree library
 LIB_PATH = os.environ.get("CGVP_LIB_PATH") or os.path.join(os.path.dirname(_HERE), "lib", "libcaster_gvp.so")
-ABI_VERSION = 30
+ABI_VERSION = 31
 # sha256 of include/caster_gvp.h with comments, blank space and the CGVP_ABI_VERSION line removed, as
 # `abi_header_digest()` computes it.  tests/test_abi.py fails when the header's declarations change
 # without CGVP_ABI_VERSION, ABI_VERSION and this digest being updated together.
-ABI_HEADER_SHA256 = "ef4411ce177566435316b9ebf051399388ee25c81d11847523b9f4fa13a0c655"
+ABI_HEADER_SHA256 = "61ec42c84e2ecff548e18c4465e3f6bbcc68d5ad71220b9adca085bcce1f028f"
 
 
 class HipLibraryError(RuntimeError):
@@ -193,6 +193,8 @@ _SIGNATURES = {
     "cgvp_gine_bwd_workspace_bytes_ex": (C.c_int64, [C.POINTER(GineCfg), _I64, _I64, _I32]),
     "cgvp_gine_backward_pass_ex": (C.c_int, [C.POINTER(GineCfg), C.POINTER(GineW), C.POINTER(GineBatch), C.c_float, _P, _P,
                                              _P, _P, _P, _P, _I32, _I32, _P]),
+    "cgvp_gine_backward_pass_eattr": (C.c_int, [C.POINTER(GineCfg), C.POINTER(GineW), C.POINTER(GineBatch), C.c_float, _P,
+                                                _P, _P, _P, _P, _P, _P, _I32, _I32, _P]),
     "cgvp_gine_backward_pass": (C.c_int, [C.POINTER(GineCfg), C.POINTER(GineW), C.POINTER(GineBatch), C.c_float, _P, _P,
                                           _P, _P, _P, _P, _I32, _P]),
     "cgvp_linear_wgrad_workspace_floats": (C.c_int64, [_I64, _I32, _I32]),

@@ -16,6 +16,7 @@ Ops
   caster_gvp::lba_encoder_backward   what autograd derives from it in the reference
   caster_gvp::gine_encoder           HomoMoleculeGNN_GINE.forward (molecule_gnn.py:254-268)
   caster_gvp::gine_encoder_backward
+  caster_gvp::gine_encoder_backward_eattr   the same plus d eattr (bond features); dispatched to only when eattr requires grad
 
 A training forward returns, next to the embeddings, ONE opaque workspace tensor `ws` (uint8): the fragment image of the
 weights the pass ran with, every stage's inputs (node rows h_l, aggregated messages dh_l), the edge-embedding store, the
@@ -604,9 +605,21 @@ def gine_encoder_backward_op(g_out: Tensor, params: List[Tensor], x: Tensor, nty
                          num_etypes, slope, dropout_p, need_x, bwd_workgroups)
 
 
+@torch.library.custom_op("caster_gvp::gine_encoder_backward_eattr", mutates_args=(), device_types="cuda")
+def gine_encoder_backward_eattr_op(g_out: Tensor, params: List[Tensor], x: Tensor, ntypes: Tensor, eattr: Tensor,
+                                   etypes: Tensor, edge_index: Tensor, csr: List[Tensor], ws: Tensor, masks: List[Tensor],
+                                   widths: List[int], num_ntypes: int, num_etypes: int, slope: float, dropout_p: float,
+                                   need_x: bool, need_eattr: bool, bwd_workgroups: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """gine_encoder_backward that also returns the gradient of the bond features: -> (gflat, g_x (empty unless need_x),
+    g_eattr [E, edge_dim] fp32 in the caller's edge order (empty unless need_eattr)).  A sibling, not a new signature: a
+    backward that does not ask for d eattr dispatches to gine_encoder_backward as it always did."""
+    return gine_backward(g_out, params, x, ntypes, eattr, etypes, edge_index, csr, ws, masks, widths, num_ntypes,
+                         num_etypes, slope, dropout_p, need_x, bwd_workgroups, need_eattr=need_eattr)
+
+
 def gine_backward(g_out, params, x, ntypes, eattr, etypes, edge_index, csr, ws, masks, widths, num_ntypes, num_etypes,
-                  slope, dropout_p, need_x, bwd_workgroups):
-    """One cgvp_gine_backward_pass."""
+                  slope, dropout_p, need_x, bwd_workgroups, need_eattr=None):
+    """One cgvp_gine_backward_pass; need_eattr not None: cgvp_gine_backward_pass_eattr, three outputs."""
     L = _lib.lib()
     nl = len(widths) - 1
     x, eattr = _f32(x, "x"), _f32(eattr, "eattr")
@@ -622,6 +635,13 @@ def gine_backward(g_out, params, x, ntypes, eattr, etypes, edge_index, csr, ws, 
     gflat = torch.empty(sum(p.numel() for p in params), **f32)        # every element is STORED by the pass's reduce
     g_x = torch.empty(N, widths[0] - num_ntypes, **f32) if need_x else None
     batch = _batch(_lib.GineBatch, (x, nt), (eattr, et), edge_index, csr, N, E)
+    if need_eattr is not None:
+        g_e = torch.empty(E, int(eattr.shape[1]), **f32) if need_eattr else None      # every row is STORED by the pass
+        _backward_pass(L.cgvp_gine_bwd_workspace_bytes_ex, (C.byref(cfg), N, E),
+                       "cgvp_gine_backward_pass_eattr", lambda ws, bws, f: L.cgvp_gine_backward_pass_eattr(
+                C.byref(cfg), warr, C.byref(batch), float(dropout_p), _mask_ptrs(masks, nl), _ptr(ws), _ptr(g), _ptr(bws),
+                _ptr(gflat), _ptr(g_x), _ptr(g_e), int(bwd_workgroups), f, _stream()), ws)
+        return (gflat, g_x if need_x else torch.empty(0, **f32), g_e if need_eattr else torch.empty(0, **f32))
     _backward_pass(L.cgvp_gine_bwd_workspace_bytes_ex, (C.byref(cfg), N, E),
                    "cgvp_gine_backward_pass_ex", lambda ws, bws, f: L.cgvp_gine_backward_pass_ex(
             C.byref(cfg), warr, C.byref(batch), float(dropout_p), _mask_ptrs(masks, nl), _ptr(ws), _ptr(g), _ptr(bws),
@@ -634,6 +654,15 @@ def _(g_out, params, x, ntypes, eattr, etypes, edge_index, csr, ws, masks, width
       dropout_p, need_x, bwd_workgroups):
     gflat = x.new_empty((sum(p.numel() for p in params),), dtype=torch.float32)
     return gflat, (x.new_empty(x.shape, dtype=torch.float32) if need_x else x.new_empty((0,), dtype=torch.float32))
+
+
+@gine_encoder_backward_eattr_op.register_fake
+def _(g_out, params, x, ntypes, eattr, etypes, edge_index, csr, ws, masks, widths, num_ntypes, num_etypes, slope,
+      dropout_p, need_x, need_eattr, bwd_workgroups):
+    empty = lambda: x.new_empty((0,), dtype=torch.float32)
+    gflat = x.new_empty((sum(p.numel() for p in params),), dtype=torch.float32)
+    return (gflat, x.new_empty(x.shape, dtype=torch.float32) if need_x else empty(),
+            x.new_empty((edge_index.shape[1], eattr.shape[1]), dtype=torch.float32) if need_eattr else empty())
 
 
 def _gine_setup(ctx, inputs, output):
@@ -655,6 +684,12 @@ def _gine_backward(ctx, g_out, g_ws, g_masks):
     x, ntypes, eattr, etypes, edge_index, ws, *rest = ctx.saved_tensors
     params, csr, masks = rest[:n_params], rest[n_params:n_params + n_csr], rest[n_params + n_csr:]
     need_x = bool(ctx.needs_input_grad[1])
+    if ctx.needs_input_grad[3]:       # d eattr asked for: the sibling op (every other backward takes the route below)
+        gflat, g_x, g_e = torch.ops.caster_gvp.gine_encoder_backward_eattr(
+            g_out.contiguous(), params, x, ntypes, eattr, etypes, edge_index, list(csr), ws, list(masks), widths,
+            num_ntypes, num_etypes, slope, dropout_p, need_x, True, GINE_BWD_WORKGROUPS)
+        return (_split_grads(gflat, ctx.shapes), g_x if need_x else None, None, g_e, None, None, [None] * n_csr, None,
+                None, None, None, None, None)
     gflat, g_x = torch.ops.caster_gvp.gine_encoder_backward(
         g_out.contiguous(), params, x, ntypes, eattr, etypes, edge_index, list(csr), ws, list(masks), widths, num_ntypes,
         num_etypes, slope, dropout_p, need_x, GINE_BWD_WORKGROUPS)
@@ -688,8 +723,6 @@ def gine_params(model, one_leaf_ok=False):
 
 def gine_encoder(model, x, ntypes, eattr, etypes, edge_index, slope, train_dropout, save_state):
     """HomoMoleculeGNN_GINE.forward through the custom op (autograd, inter-layer dropout when training)."""
-    if eattr.requires_grad:
-        raise NotImplementedError("gradients w.r.t. bond features are not produced by the backward kernels")
     p = float(model.dropout_rate) if train_dropout else 0.0
     br, (x, eattr) = _bridge_for((x, eattr))
     if br is not None:

@@ -15,7 +15,8 @@ shapes.  `GraphedEncoderStep` keeps one captured step per SHAPE BUCKET:
     by (seed, offset, layer, row, channel), so the real rows draw the same factors as in an unpadded eager step.
 
 The outputs (embeddings of the real rows, every weight gradient) are the graph's static tensors: consume them (optimizer
-step, all-reduce) before the next `run` of the same bucket.  Opt-in: the nn.Module API is untouched.
+step, all-reduce) before the next `run` of the same bucket.  The inputs are staged copies, so a captured step returns no
+input gradients (d x, d eattr: the eager nn.Module path does).  Opt-in: the nn.Module API is untouched.
 """
 from __future__ import annotations
 

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CGVP_ABI_VERSION 30
+#define CGVP_ABI_VERSION 31
 #define CGVP_ERR_BAD_ARG (-1)
 #define CGVP_ERR_UNSUPPORTED_DIMS (-2)
 /* the call would add floats in arrival order while the deterministic mode is on (CGVP_BWD_DETERMINISTIC in `flags`, or
@@ -590,6 +590,15 @@ int cgvp_gine_backward_pass_ex(const cgvp_gine_cfg* cfg, const cgvp_gine_w* w, c
                                float dropout_p, const float* const* masks, const void* fwd_workspace, const float* g_out,
                                void* bwd_workspace, float* grad_flat, float* g_x, int32_t max_workgroups, int32_t flags,
                                void* stream);
+/* cgvp_gine_backward_pass_ex that also returns the gradient w.r.t. the raw bond features: g_eattr [E][edge_dim] fp32 in
+ * the ORIGINAL edge order (the layers' contributions summed; the bond TYPES are integers and have none), or NULL to skip
+ * -- then it is cgvp_gine_backward_pass_ex, launch for launch.  Every row is STORED (no zero fill, no float atomics: the
+ * last layer's launch stores, the earlier layers' launches add), so the result is as reproducible as the d x it is computed
+ * beside.  Needs no workspace: the queries above size both calls. */
+int cgvp_gine_backward_pass_eattr(const cgvp_gine_cfg* cfg, const cgvp_gine_w* w, const cgvp_gine_batch* batch,
+                                  float dropout_p, const float* const* masks, const void* fwd_workspace, const float* g_out,
+                                  void* bwd_workspace, float* grad_flat, float* g_x, float* g_eattr,
+                                  int32_t max_workgroups, int32_t flags, void* stream);
 
 /* ------------------------------------------------------------ ROW-WISE LINEAR LAYERS OF THE HEAD: weight gradients
  * The joint head applies nn.Linear layers to every residue / atom row (joint_gnn.py:188-198, :376-389).  Their weight and
