@@ -842,52 +842,33 @@ int launch_fwd(GineFArgs& a, hipStream_t st) {
   }();
   const int G = (int)(wgs < 1 ? 1 : (wgs > cap ? cap : wgs));
   const size_t lds = (size_t)((Q::GE::NFRAG + Q::G0::NFRAG + Q::G1::NFRAG) * 64 + Q::CINP + CHID + COUT + GF_WPB * Q::ROWS) * sizeof(float);
-  CGVP_SET_DYN_LDS_ONCE((gine_quad_fwd_kernel<CIN, CHID, COUT, NT, NET, ED>), lds);
-  hipLaunchKernelGGL((gine_quad_fwd_kernel<CIN, CHID, COUT, NT, NET, ED>), dim3(G), dim3(GF_TPB), lds, st, a);
-  return 0;
+  return launch<gine_quad_fwd_kernel<CIN, CHID, COUT, NT, NET, ED>>(dim3(G), dim3(GF_TPB), lds, st, a);
 }
 
+// SAVED (the forward's aggregates are given) x STORE (deterministic mode: needs SAVED) x EG (bond-feature gradient: same
+// grid, one more fragment group in LDS)
 template <int CIN, int CHID, int COUT, int NT, int NET, int ED>
-int launch(GineQArgs& a, int cap, int* rows, int* row_len, hipStream_t st) {
+int launch_bwd(GineQArgs& a, int cap, int* rows, int* row_len, hipStream_t st) {
   typedef GineQ<CIN, CHID, COUT, NT, NET, ED> Q;
-  constexpr int GQ_WPB = Q::WPB, GQ_TPB = Q::TPB;
   const int64_t tiles = (a.N + TILE - 1) / TILE;
-  int64_t wgs = (tiles + GQ_WPB - 1) / GQ_WPB;
+  int64_t wgs = (tiles + Q::WPB - 1) / Q::WPB;
   const int G = (int)(wgs < 1 ? 1 : (wgs > cap ? cap : wgs));
-  if (a.g_eattr) {             // the same three forms with the bond-feature gradient: same grid, one more fragment group in LDS
-    typedef GineQ<CIN, CHID, COUT, NT, NET, ED, true> QE;
-    static_assert(QE::TPB == Q::TPB && QE::L_SIZE == Q::L_SIZE, "same workgroup shape and slab row");
-    const size_t ldse = (size_t)QE::LDS_FLOATS * sizeof(float);
-    if (a.g_edge) {
-      if (!(a.agg_in && a.pos_in)) return CGVP_ERR_NONDETERMINISTIC;
-      CGVP_SET_DYN_LDS_ONCE((gine_quad_bwd_kernel<CIN, CHID, COUT, NT, NET, ED, true, true, true>), ldse);
-      hipLaunchKernelGGL((gine_quad_bwd_kernel<CIN, CHID, COUT, NT, NET, ED, true, true, true>), dim3(G), dim3(GQ_TPB), ldse, st, a);
-    } else if (a.agg_in && a.pos_in) {
-      CGVP_SET_DYN_LDS_ONCE((gine_quad_bwd_kernel<CIN, CHID, COUT, NT, NET, ED, true, false, true>), ldse);
-      hipLaunchKernelGGL((gine_quad_bwd_kernel<CIN, CHID, COUT, NT, NET, ED, true, false, true>), dim3(G), dim3(GQ_TPB), ldse, st, a);
-    } else {
-      CGVP_SET_DYN_LDS_ONCE((gine_quad_bwd_kernel<CIN, CHID, COUT, NT, NET, ED, false, false, true>), ldse);
-      hipLaunchKernelGGL((gine_quad_bwd_kernel<CIN, CHID, COUT, NT, NET, ED, false, false, true>), dim3(G), dim3(GQ_TPB), ldse, st, a);
-    }
-    *rows = G;
-    *row_len = Q::L_SIZE;
-    return 0;
-  }
-  const size_t lds = (size_t)Q::LDS_FLOATS * sizeof(float);
-  if (a.g_edge) {              // deterministic mode: the SAVED path only
-    if (!(a.agg_in && a.pos_in)) return CGVP_ERR_NONDETERMINISTIC;
-    CGVP_SET_DYN_LDS_ONCE((gine_quad_bwd_kernel<CIN, CHID, COUT, NT, NET, ED, true, true>), lds);
-    hipLaunchKernelGGL((gine_quad_bwd_kernel<CIN, CHID, COUT, NT, NET, ED, true, true>), dim3(G), dim3(GQ_TPB), lds, st, a);
-  } else if (a.agg_in && a.pos_in) {
-    CGVP_SET_DYN_LDS_ONCE((gine_quad_bwd_kernel<CIN, CHID, COUT, NT, NET, ED, true>), lds);
-    hipLaunchKernelGGL((gine_quad_bwd_kernel<CIN, CHID, COUT, NT, NET, ED, true>), dim3(G), dim3(GQ_TPB), lds, st, a);
-  } else {
-    CGVP_SET_DYN_LDS_ONCE((gine_quad_bwd_kernel<CIN, CHID, COUT, NT, NET, ED, false>), lds);
-    hipLaunchKernelGGL((gine_quad_bwd_kernel<CIN, CHID, COUT, NT, NET, ED, false>), dim3(G), dim3(GQ_TPB), lds, st, a);
-  }
+  const bool saved = a.agg_in && a.pos_in;
+  if (a.g_edge && !saved) return CGVP_ERR_NONDETERMINISTIC;
   *rows = G;
   *row_len = Q::L_SIZE;
-  return 0;
+  return with_flag(saved, [&](auto saved_) {
+    return with_flag(a.g_edge != nullptr, [&](auto store_) {
+      return with_flag(a.g_eattr != nullptr, [&](auto eg_) {
+        constexpr bool SAVED = decltype(saved_)::value, STORE = decltype(store_)::value, EG = decltype(eg_)::value;
+        typedef GineQ<CIN, CHID, COUT, NT, NET, ED, EG> QE;
+        static_assert(QE::TPB == Q::TPB && QE::L_SIZE == Q::L_SIZE, "same workgroup shape and slab row");
+        if constexpr (STORE && !SAVED) return CGVP_ERR_NONDETERMINISTIC;
+        else return launch<gine_quad_bwd_kernel<CIN, CHID, COUT, NT, NET, ED, SAVED, STORE, EG>>(
+                 dim3(G), dim3(Q::TPB), (size_t)QE::LDS_FLOATS * sizeof(float), st, a);
+      });
+    });
+  });
 }
 
 }  // namespace
@@ -905,10 +886,10 @@ int gine_bwd(int cin, int chid, int cout, int nt, int net, int ed, const float* 
   GineQArgs a{x, ntypes, eattr, etypes, rowptr, eperm, esrc, edst, N, w->eps, w->we, w->be, w->w0, w->b0,
               w->w1, w->b1, slope, mask, rng, g_out, g_x, slab, agg_in, pos_in, g_edge, g_self, g_eattr, eattr_accum};
   // compiled for the layer shapes of HomoMoleculeGNN_GINE in CASTER-DTA (molecule_gnn.py:240-250)
-  if (cin == 52 && chid == 16 && cout == 16 && nt == 11 && net == 5 && ed == 9) return launch<52, 16, 16, 11, 5, 9>(a, cap, rows, row_len, st);
-  if (cin == 52 && chid == 16 && cout == 16 && nt == 0 && net == 5 && ed == 9) return launch<52, 16, 16, 0, 5, 9>(a, cap, rows, row_len, st);   // nn.Embedding atom types (11-wide), materialised by the host
-  if (cin == 16 && chid == 64 && cout == 64 && nt == 0 && net == 5 && ed == 9) return launch<16, 64, 64, 0, 5, 9>(a, cap, rows, row_len, st);
-  if (cin == 16 && chid == 16 && cout == 16 && nt == 0 && net == 5 && ed == 9) return launch<16, 16, 16, 0, 5, 9>(a, cap, rows, row_len, st);   // middle layers of deeper stacks
+  if (cin == 52 && chid == 16 && cout == 16 && nt == 11 && net == 5 && ed == 9) return launch_bwd<52, 16, 16, 11, 5, 9>(a, cap, rows, row_len, st);
+  if (cin == 52 && chid == 16 && cout == 16 && nt == 0 && net == 5 && ed == 9) return launch_bwd<52, 16, 16, 0, 5, 9>(a, cap, rows, row_len, st);   // nn.Embedding atom types (11-wide), materialised by the host
+  if (cin == 16 && chid == 64 && cout == 64 && nt == 0 && net == 5 && ed == 9) return launch_bwd<16, 64, 64, 0, 5, 9>(a, cap, rows, row_len, st);
+  if (cin == 16 && chid == 16 && cout == 16 && nt == 0 && net == 5 && ed == 9) return launch_bwd<16, 16, 16, 0, 5, 9>(a, cap, rows, row_len, st);   // middle layers of deeper stacks
   return CGVP_ERR_UNSUPPORTED_DIMS;
 }
 

@@ -7,8 +7,8 @@
 #include "gvp_math.h"
 #include "gvp_rng.h"
 
-// Tile policy index the launchers in namespace quad take (their `bf16` parameter): activation storage type x layer kind
-// (cgvp_dims.storage / cgvp_dims.layer_kind; gvp_quad.h LayerKind).  bf16 storage exists for CASTER-DTA's layers only.
+// Tile policy index the launchers in namespace quad take: activation storage type x layer kind (cgvp_dims.storage /
+// cgvp_dims.layer_kind; gvp_quad.h LayerKind).  bf16 storage exists for CASTER-DTA's layers only.
 constexpr int POLICY_F32 = 0, POLICY_BF16 = 1, POLICY_GVPDEF = 2, POLICY_LINEAR = 3;
 
 // Float offsets of the per-kernel slices inside the fragment image.
@@ -22,39 +22,73 @@ struct QuadOffsets {
 #endif
 constexpr int kBwdMaxGrid = CGVP_BWD_MAX_GRID;    // persistent workgroups of the backward kernels (one per CU) = slab rows per stage
 
-// hipFuncAttributeMaxDynamicSharedMemorySize of a kernel, set ONCE per kernel and device instead of before every launch
-// (hipFuncSetAttribute is a host call of tens of microseconds; a backward pass made 13 of them).  One static flag word per
-// expansion site, one bit per device: idempotent, benign process state (the attribute itself is process state of the runtime).
 #include <atomic>
-#define CGVP_SET_DYN_LDS_ONCE(FN, BYTES)                                                                                      \
-  do {                                                                                                                        \
-    static std::atomic<uint64_t> cgvp_done_{0};                                                                               \
-    int cgvp_dev_ = 0;                                                                                                        \
-    (void)hipGetDevice(&cgvp_dev_);                                                                                           \
-    const uint64_t cgvp_bit_ = 1ull << (cgvp_dev_ & 63);                                                                      \
-    if (!(cgvp_done_.load(std::memory_order_acquire) & cgvp_bit_)) {                                                          \
-      if (hipError_t cgvp_err_ = hipFuncSetAttribute(reinterpret_cast<const void*>(FN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BYTES))) \
-        return (int)cgvp_err_;                                                                                                \
-      cgvp_done_.fetch_or(cgvp_bit_, std::memory_order_release);                                                              \
-    }                                                                                                                         \
-  } while (0)
+#include <type_traits>
+
+// One launch of `Kernel`; returns 0, a CGVP_ERR_* code or the hipError_t of a failed attribute call.  A launch that needs
+// more dynamic LDS than the 64 KB every kernel may use raises hipFuncAttributeMaxDynamicSharedMemorySize to `reserve`
+// bytes first, ONCE per kernel and device (hipFuncSetAttribute is a host call of tens of microseconds; a backward pass
+// made 13 of them): the static below exists per instantiation = per kernel and holds the bytes set on each device.  A
+// later launch of the same kernel that asks for more than was set is refused instead of faulting on the device.
+template <auto Kernel, class... A>
+int launch_reserving(dim3 grid, dim3 block, size_t lds, size_t reserve, hipStream_t st, const A&... args) {
+  if (lds > 64 * 1024) {
+    static std::atomic<int> set_bytes[64];      // zero = not set on that device yet; idempotent, benign process state
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::atomic<int>& set = set_bytes[dev & 63];
+    int have = set.load(std::memory_order_acquire);
+    if (!have && lds <= reserve) {
+      if (hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)reserve))
+        return (int)err;
+      set.store(have = (int)reserve, std::memory_order_release);
+    }
+    if (lds > (size_t)have) return CGVP_ERR_BAD_ARG;
+  }
+  hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
+  return 0;
+}
+// the usual case: the kernel has ONE dynamic LDS size
+template <auto Kernel, class... A>
+int launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... args) {
+  return launch_reserving<Kernel>(grid, block, lds, lds, st, args...);
+}
+
+// Runtime value -> compile-time tag of a generic lambda, so that every combination of kernel template flags is written once.
+// with_policy: `f(Tag<ST>{})` for the storage tag type ST of a tile policy index; KINDS says whether the two layer-kind
+// policies exist for the kernel (they are not instantiated otherwise).  with_flag: `f(std::bool_constant<b>{})`.
+namespace gq { struct bf16s; struct f32_gvpdef; struct f32_linear; }
+template <class T> struct Tag { using type = T; };
+template <class ST> constexpr bool is_layer_kind = std::is_same_v<ST, gq::f32_gvpdef> || std::is_same_v<ST, gq::f32_linear>;
+template <bool KINDS, class F>
+int with_policy(int policy, F&& f) {
+  if (policy == POLICY_F32) return f(Tag<float>{});
+  if (policy == POLICY_BF16) return f(Tag<gq::bf16s>{});
+  if constexpr (KINDS) {
+    if (policy == POLICY_GVPDEF) return f(Tag<gq::f32_gvpdef>{});
+    if (policy == POLICY_LINEAR) return f(Tag<gq::f32_linear>{});
+  }
+  return CGVP_ERR_UNSUPPORTED_DIMS;
+}
+template <class F>
+int with_flag(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
 
 namespace quad {
 int offsets(int nt_node, int nt_edge, int num_convs, QuadOffsets* o);
 int prepare(const gvp::EncLayout& L, int num_convs, int packed_bf16, const float* params, float* image, hipStream_t st);
 int node_embed(int nt_node, const float* img, const float* x_s, const float* x_v, const int64_t* ntypes,
-               int64_t N, float* h, unsigned long long* rng_state, unsigned long long* rng_out, int bf16, hipStream_t st);
-int pass_begin(const gvp::EncLayout& L, int num_convs, int bf16, const float* params, float* image, const float* x_s,
+               int64_t N, float* h, unsigned long long* rng_state, unsigned long long* rng_out, int policy, hipStream_t st);
+int pass_begin(const gvp::EncLayout& L, int num_convs, int policy, const float* params, float* image, const float* x_s,
                const float* x_v, const int64_t* ntypes, int64_t N, float* h, unsigned long long* rng_state,
                unsigned long long* rng_out, const int64_t* edge_index, int64_t E, int32_t* counters, hipStream_t st);
 int conv(int nt_edge, const float* img, const float* h, const float* e_s, const float* e_v,
          const int64_t* etypes, const int32_t* rowptr, const int32_t* eperm, const int32_t* esrc,
          const int32_t* edst, int64_t N, int64_t E, int mean, float* dh, int fuse, const float* img_node,
          const float* img_head, float* h_out, float* out, const float* mask0, const float* mask1, gvp::RngArgs rng,
-         const float* e_in, float* e_out, int bf16, hipStream_t st);
+         const float* e_in, float* e_out, int policy, hipStream_t st);
 int node_update(const float* img_node, const float* img_head, const float* h, const float* dh, int64_t N,
                 int with_head, float* h_out, float* out, const float* mask0, const float* mask1, gvp::RngArgs rng,
-                int bf16, hipStream_t st);
+                int policy, hipStream_t st);
 
 // ---- backward (gvp_quad_bwd_kernels.hip).  Weight gradients are written as one
 // partial block per workgroup into `slab` ([grid][block floats]); `grid` returns
@@ -62,17 +96,17 @@ int node_update(const float* img_node, const float* img_head, const float* h, co
 int node_update_bwd(const float* img_node, const float* imgT_node, const float* h, const float* dh,
                     const float* mask0, const float* mask1, gvp::RngArgs rng, const float* g_up0, const float* g_up1,
                     const float* g_up2, int64_t N, float* g_dh, float* g_h, float* zero_rows, float* slab, int* grid,
-                    int bf16, hipStream_t st);
+                    int policy, hipStream_t st);
 int head_bwd(const float* img_head, const float* imgT_head, const float* h_out, const float* g_out, int64_t N,
-             float* g_h_out, float* slab, int* grid, int bf16, hipStream_t st);
+             float* g_h_out, float* slab, int* grid, int policy, hipStream_t st);
 // head_bwd + node_update_bwd of the last layer as ONE launch (g_h_out doubles as the node stage's upstream gradient)
 int node_head_bwd(const float* img_head, const float* imgT_head, const float* h_out, const float* g_out, float* g_h_out,
                   float* head_slab, const float* img_node, const float* imgT_node, const float* h, const float* dh,
                   const float* mask0, const float* mask1, gvp::RngArgs rng, int64_t N, float* g_dh, float* g_h,
-                  float* zero_rows, float* slab, int* grid, int bf16, hipStream_t st);
+                  float* zero_rows, float* slab, int* grid, int policy, hipStream_t st);
 int conv_bwd(int nt_edge, const float* img, const float* imgT, const float* h, const float* e_emb,
              const int32_t* rowptr, const int32_t* esrc, const int32_t* edst, int64_t N, int64_t E, int mean,
-             const float* g_dh, float* g_src, float* g_dst, float* g_e, float* slab, int* grid, int bf16, hipStream_t st,
+             const float* g_dh, float* g_src, float* g_dst, float* g_e, float* slab, int* grid, int policy, hipStream_t st,
              float* g_edge = nullptr, float* slot = nullptr);
 // ---- deterministic mode (CGVP_BWD_DETERMINISTIC): store-then-sum instead of float atomics
 // conv_bwd with g_edge / slot: d h[src] rows -> g_edge [E][28] at their sorted positions, boundary rows -> slot
@@ -97,11 +131,11 @@ bool deterministic_env();
 // backward of gvp_edge + LayerNorm from the summed d(edge embedding) of the conv layers (weight gradients only)
 int edge_embed_bwd(int nt_edge, const float* img, const float* imgT, const float* e_s, const float* e_v,
                    const int64_t* etypes, const int32_t* eperm, int64_t E, const float* const* g_e, int n_g,
-                   float* g_e_s, float* g_e_v, float* slab, int* grid, int bf16, hipStream_t st);
+                   float* g_e_s, float* g_e_v, float* slab, int* grid, int policy, hipStream_t st);
 constexpr int kEdgeRow = 36;              // floats per edge of the stored edge embedding: [e_s 32 | e_v 3 | pad]
 int node_embed_bwd(int nt_node, const float* img, const float* imgT, const float* x_s, const float* x_v,
                    const int64_t* ntypes, int64_t N, const float* g_up0, const float* g_up1, const float* g_up2,
-                   float* g_x_s, float* g_x_v, float* slab, int* grid, int bf16, hipStream_t st);
+                   float* g_x_s, float* g_x_v, float* slab, int* grid, int policy, hipStream_t st);
 // GINE layer backward on 16-atom MFMA tiles (gine_quad_kernels.hip): one slab row per workgroup
 // (`rows` x `row_len` floats, state_dict order of the layer).
 constexpr int kGineBwdMaxGrid = 256;      // upper bound (workspace sizing)
@@ -121,7 +155,9 @@ int gine_fwd(int cin, int chid, int cout, int nt, int net, int ed, const float* 
 int reduce_slab(const float* slab, int rows, int stride, int col0, int len, float* dst, hipStream_t st);
 int reduce_segments(const cgvp_segment* segs, int nsegs, float* grad_params, hipStream_t st, int overwrite = 0,
                     bool store_only = false);
-int bwd_block_sizes(int nt_node, int nt_edge, int* emb, int* conv_edge, int* conv_total, int* node, int* head);
+// floats of one slab row (= one workgroup's weight-gradient block) of each backward stage
+struct BwdBlocks { int emb, conv_edge, conv_total, node, head; };
+int bwd_block_sizes(int nt_node, int nt_edge, BwdBlocks* b);
 // gvp_kernels.hip
 void zero_words(void* p, size_t words, hipStream_t s);     // the library's own zero fill (never hipMemsetAsync: see gvp_kernels.hip)
 int csr_build(const int64_t* edge_index, int64_t N, int64_t E, int32_t* rowptr, int32_t* eperm, int32_t* esrc,

@@ -59,6 +59,21 @@ inline int launch_status() {
   return e == hipSuccess ? 0 : (int)e;
 }
 
+// what every fine-grained backward entry point looks up first: the image offsets and the slab row sizes of the layout
+struct BwdLookup : QuadOffsets { quad::BwdBlocks blk; };
+inline int bwd_lookup(const cgvp_layout& l, BwdLookup* o) {
+  if (int rc = quad::offsets(l.nt_node, l.nt_edge, num_convs_of(l), o)) return rc;
+  return quad::bwd_block_sizes(l.nt_node, l.nt_edge, &o->blk);
+}
+// ... and what it ends with: the slab segments go to the caller (who reduces them with the rest of the pass) or are
+// reduced into grad_params now
+inline int emit_segments(const cgvp_segment* sg, int n, cgvp_segment* segs, int32_t* nsegs, float* grad_params,
+                         hipStream_t st, int overwrite = 0, bool store_only = false) {
+  if (segs && nsegs) { for (int k = 0; k < n; ++k) segs[k] = sg[k]; *nsegs = n; }
+  else quad::reduce_segments(sg, n, grad_params, st, overwrite, store_only);
+  return launch_status();
+}
+
 // ------------------------------------------------------------------ CSR build
 // Stable counting sort of the edges by target in four launches:
 //   count  : cnt[dst] += 1                                     (int atomics, one thread per edge)
@@ -1000,11 +1015,11 @@ int cgvp_node_update_fwd_train(const cgvp_dims* dims, const cgvp_layout* layout,
 int64_t cgvp_bwd_workspace_floats(const cgvp_dims* dims, const cgvp_layout* layout) {
   if (int rc = check_dims(dims)) return rc;
   if (!layout) return CGVP_ERR_BAD_ARG;
-  int emb, ce, ct, nd, hd;
-  if (int rc = quad::bwd_block_sizes(layout->nt_node, layout->nt_edge, &emb, &ce, &ct, &nd, &hd)) return rc;
-  int mx = emb > ct ? emb : ct;
-  mx = mx > nd + hd ? mx : nd + hd;
-  mx = mx > 2 * ce ? mx : 2 * ce;            // the edge stage runs two workgroups per CU (2 x kBwdMaxGrid slab rows)
+  quad::BwdBlocks b;
+  if (int rc = quad::bwd_block_sizes(layout->nt_node, layout->nt_edge, &b)) return rc;
+  int mx = b.emb > b.conv_total ? b.emb : b.conv_total;
+  mx = mx > b.node + b.head ? mx : b.node + b.head;
+  mx = mx > 2 * b.conv_edge ? mx : 2 * b.conv_edge;            // the edge stage runs two workgroups per CU (2 x kBwdMaxGrid slab rows)
   return (int64_t)kBwdMaxGrid * mx;
 }
 
@@ -1024,12 +1039,11 @@ int cgvp_node_update_bwd(const cgvp_dims* dims, const cgvp_layout* layout, const
   if (with_head && dims->layer_kind != CGVP_LAYER_GATED) return CGVP_ERR_UNSUPPORTED_DIMS;     // the head is CASTER-DTA's
   const void* al[] = {h, dh, mask0, mask1, h_out, g_out, g_up0, g_up1, g_up2, g_dh, g_h, zero_out};
   for (const void* q : al) if ((uintptr_t)q & 15) return CGVP_ERR_BAD_ARG;
-  QuadOffsets o;
-  if (int rc = quad::offsets(layout->nt_node, layout->nt_edge, nc, &o)) return rc;
-  int emb, ce, ct, nd, hd, grid = 0, hgrid = 0;
-  if (int rc = quad::bwd_block_sizes(layout->nt_node, layout->nt_edge, &emb, &ce, &ct, &nd, &hd)) return rc;
+  BwdLookup o;
+  if (int rc = bwd_lookup(*layout, &o)) return rc;
+  int grid = 0, hgrid = 0;
   hipStream_t st = (hipStream_t)stream;
-  float* head_slab = workspace + (size_t)kBwdMaxGrid * nd;
+  float* head_slab = workspace + (size_t)kBwdMaxGrid * o.blk.node;
   // CGVP_SPLIT_HEAD_BWD=1 keeps the head stage in a launch of its own (A/B switch; the results are the same)
   static const bool split_head = [] { const char* e = getenv("CGVP_SPLIT_HEAD_BWD"); return e && e[0] == '1'; }();
   if (with_head && !split_head) {
@@ -1049,12 +1063,9 @@ int cgvp_node_update_bwd(const cgvp_dims* dims, const cgvp_layout* layout, const
                                      workspace, &grid, policy_of(dims), st)) return rc;
   }
   const int node_len = conv_ff1() + LFf1::size(0) - conv_ln0();          // norm.0 .. end of ff_func.1
-  cgvp_segment sg[2] = {{workspace, grid, nd, 0, node_len, layout->conv0 + layer * layout->conv_stride + conv_ln0()},
-                        {head_slab, hgrid, hd, 0, layout->total - layout->ln_out, layout->ln_out}};
-  const int n = with_head ? 2 : 1;
-  if (segs && nsegs) { for (int k = 0; k < n; ++k) segs[k] = sg[k]; *nsegs = n; }
-  else quad::reduce_segments(sg, n, grad_params, st);
-  return launch_status();
+  cgvp_segment sg[2] = {{workspace, grid, o.blk.node, 0, node_len, layout->conv0 + layer * layout->conv_stride + conv_ln0()},
+                        {head_slab, hgrid, o.blk.head, 0, layout->total - layout->ln_out, layout->ln_out}};
+  return emit_segments(sg, with_head ? 2 : 1, segs, nsegs, grad_params, st);
 }
 
 int cgvp_conv_bwd(const cgvp_dims* dims, const cgvp_layout* layout, const float* image, int32_t layer,
@@ -1084,10 +1095,9 @@ int quad::conv_bwd_entry(const cgvp_dims* dims, const cgvp_layout* layout, const
   if (E > 0 && (!e_emb || !g_e || !esrc || !edst)) return CGVP_ERR_BAD_ARG;
   const void* al[] = {h, e_emb, g_dh, g_src, g_dst, g_e};
   for (const void* q : al) if ((uintptr_t)q & 15) return CGVP_ERR_BAD_ARG;
-  QuadOffsets o;
-  if (int rc = quad::offsets(layout->nt_node, layout->nt_edge, nc, &o)) return rc;
-  int emb, ce, ct, nd, hd, grid = 0;
-  if (int rc = quad::bwd_block_sizes(layout->nt_node, layout->nt_edge, &emb, &ce, &ct, &nd, &hd)) return rc;
+  BwdLookup o;
+  if (int rc = bwd_lookup(*layout, &o)) return rc;
+  int grid = 0;
   hipStream_t st = (hipStream_t)stream;
   if (!g_src_zeroed && !det) {
     zero_words(g_src, (size_t)N * ROW, st);
@@ -1099,10 +1109,8 @@ int quad::conv_bwd_entry(const cgvp_dims* dims, const cgvp_layout* layout, const
   if (det)
     if (int rc = quad::src_sum(ROW, det->rows, nullptr, det->sptr, det->spos, rowptr, det->slot, (int64_t)grid * 8, N, g_src, st))
       return rc;
-  cgvp_segment sg[1] = {{workspace, grid, ct, 0, conv_ln0(), layout->conv0 + layer * layout->conv_stride}};
-  if (segs && nsegs) { segs[0] = sg[0]; *nsegs = 1; }
-  else quad::reduce_segments(sg, 1, grad_params, st, det ? 1 : 0, det != nullptr);
-  return launch_status();
+  const cgvp_segment sg{workspace, grid, o.blk.conv_total, 0, conv_ln0(), layout->conv0 + layer * layout->conv_stride};
+  return emit_segments(&sg, 1, segs, nsegs, grad_params, st, det ? 1 : 0, det != nullptr);
 }
 
 extern "C" {
@@ -1153,11 +1161,9 @@ int cgvp_edge_embed_bwd(const cgvp_dims* dims, const cgvp_layout* layout, const 
   if (!e_s || !e_v || !eperm || (layout->nt_edge > 0 && !etypes)) return CGVP_ERR_BAD_ARG;
   if ((uintptr_t)e_s & 15) return CGVP_ERR_BAD_ARG;
   for (int l = 0; l < num_g; ++l) if (!g_e[l] || ((uintptr_t)g_e[l] & 15)) return CGVP_ERR_BAD_ARG;
-  const int nc = num_convs_of(*layout);
-  QuadOffsets o;
-  if (int rc = quad::offsets(layout->nt_node, layout->nt_edge, nc, &o)) return rc;
-  int emb, ce, ct, nd, hd, grid = 0;
-  if (int rc = quad::bwd_block_sizes(layout->nt_node, layout->nt_edge, &emb, &ce, &ct, &nd, &hd)) return rc;
+  BwdLookup o;
+  if (int rc = bwd_lookup(*layout, &o)) return rc;
+  int grid = 0;
   hipStream_t st = (hipStream_t)stream;
   if (g_e_s) {        // edges the CSR build dropped (endpoint out of range) are in no tile: their rows stay zero
     quad::zero_words(g_e_s, (size_t)E * EDGE_IN_S, st);
@@ -1166,10 +1172,8 @@ int cgvp_edge_embed_bwd(const cgvp_dims* dims, const cgvp_layout* layout, const 
   // gvp_edge's fragments are the head of every conv slice (identical in all layers): layer 0's is used
   if (int rc = quad::edge_embed_bwd(layout->nt_edge, image + o.conv0, image + o.convT0, e_s, e_v, etypes, eperm, E, g_e,
                                     num_g, g_e_s, g_e_v, workspace, &grid, policy_of(dims), st)) return rc;
-  cgvp_segment sg[1] = {{workspace, grid, ce, 0, layout->conv0 - layout->edge_gvp, layout->edge_gvp}};
-  if (segs && nsegs) { segs[0] = sg[0]; *nsegs = 1; }
-  else quad::reduce_segments(sg, 1, grad_params, st);
-  return launch_status();
+  const cgvp_segment sg{workspace, grid, o.blk.conv_edge, 0, layout->conv0 - layout->edge_gvp, layout->edge_gvp};
+  return emit_segments(&sg, 1, segs, nsegs, grad_params, st);
 }
 
 int cgvp_node_embed_bwd(const cgvp_dims* dims, const cgvp_layout* layout, const float* image, const float* x_s,
@@ -1182,17 +1186,14 @@ int cgvp_node_embed_bwd(const cgvp_dims* dims, const cgvp_layout* layout, const 
   if (!x_s || !x_v || (layout->nt_node > 0 && !ntypes) || ((g_x_s == nullptr) != (g_x_v == nullptr))) return CGVP_ERR_BAD_ARG;
   const void* al[] = {g_up0, g_up1, g_up2};
   for (const void* q : al) if ((uintptr_t)q & 15) return CGVP_ERR_BAD_ARG;
-  QuadOffsets o;
-  if (int rc = quad::offsets(layout->nt_node, layout->nt_edge, num_convs_of(*layout), &o)) return rc;
-  int emb, ce, ct, nd, hd, grid = 0;
-  if (int rc = quad::bwd_block_sizes(layout->nt_node, layout->nt_edge, &emb, &ce, &ct, &nd, &hd)) return rc;
+  BwdLookup o;
+  if (int rc = bwd_lookup(*layout, &o)) return rc;
+  int grid = 0;
   hipStream_t st = (hipStream_t)stream;
   if (int rc = quad::node_embed_bwd(layout->nt_node, image + o.emb, image + o.embT, x_s, x_v, ntypes, N, g_up0, g_up1,
                                     g_up2, g_x_s, g_x_v, workspace, &grid, policy_of(dims), st)) return rc;
-  cgvp_segment sg[1] = {{workspace, grid, emb, 0, layout->edge_gvp - layout->node_gvp, layout->node_gvp}};
-  if (segs && nsegs) { segs[0] = sg[0]; *nsegs = 1; }
-  else quad::reduce_segments(sg, 1, grad_params, st);
-  return launch_status();
+  const cgvp_segment sg{workspace, grid, o.blk.emb, 0, layout->edge_gvp - layout->node_gvp, layout->node_gvp};
+  return emit_segments(&sg, 1, segs, nsegs, grad_params, st);
 }
 
 int cgvp_gine_conv_fwd(const float* x, const int64_t* ntypes, int32_t num_ntypes, const float* eattr,

@@ -1419,14 +1419,14 @@ inline int grid_for(int64_t tiles) {          // workgroups = slab rows; tiles g
 
 namespace quad {
 
-int bwd_block_sizes(int nt_node, int nt_edge, int* emb, int* conv_edge, int* conv_total, int* node, int* head) {
-  if (nt_node == 0) *emb = EmbBlk<0>::SIZE; else if (nt_node == 20) *emb = EmbBlk<20>::SIZE;
-  else if (nt_node == 21) *emb = EmbBlk<21>::SIZE; else return CGVP_ERR_UNSUPPORTED_DIMS;
-  if (nt_edge == 0) { *conv_edge = EdgeBlk<0>::SIZE; *conv_total = ConvBlk<0>::SIZE; }     // edge_bwd / conv_bwd blocks
-  else if (nt_edge == 1) { *conv_edge = EdgeBlk<1>::SIZE; *conv_total = ConvBlk<1>::SIZE; }
+int bwd_block_sizes(int nt_node, int nt_edge, BwdBlocks* b) {
+  if (nt_node == 0) b->emb = EmbBlk<0>::SIZE; else if (nt_node == 20) b->emb = EmbBlk<20>::SIZE;
+  else if (nt_node == 21) b->emb = EmbBlk<21>::SIZE; else return CGVP_ERR_UNSUPPORTED_DIMS;
+  if (nt_edge == 0) { b->conv_edge = EdgeBlk<0>::SIZE; b->conv_total = ConvBlk<0>::SIZE; }     // edge_bwd / conv_bwd blocks
+  else if (nt_edge == 1) { b->conv_edge = EdgeBlk<1>::SIZE; b->conv_total = ConvBlk<1>::SIZE; }
   else return CGVP_ERR_UNSUPPORTED_DIMS;
-  *node = NODE_GB;
-  *head = HEAD_GB;
+  b->node = NODE_GB;
+  b->head = HEAD_GB;
   return 0;
 }
 
@@ -1483,85 +1483,52 @@ int reduce_slab(const float* slab, int rows, int stride, int col0, int len, floa
   return 0;
 }
 
-// one launch of a backward kernel in the requested activation storage type
-#define BWD_LAUNCH(KERNEL, G, TPB_, LDS_, ...)                                                                              \
-  do {                                                                                                                        \
-    if (bf16) {                                                                                                               \
-      CGVP_SET_DYN_LDS_ONCE(KERNEL(bf16s), LDS_);                                                                             \
-      hipLaunchKernelGGL((KERNEL(bf16s)), dim3(G), dim3(TPB_), (LDS_), st, __VA_ARGS__);                                            \
-    } else {                                                                                                                  \
-      CGVP_SET_DYN_LDS_ONCE(KERNEL(float), LDS_);                                                                             \
-      hipLaunchKernelGGL((KERNEL(float)), dim3(G), dim3(TPB_), (LDS_), st, __VA_ARGS__);                                            \
-    }                                                                                                                         \
-  } while (0)
-
-// the same for the two kernels that exist for every layer kind (`bf16` = tile policy index, gvp_internal.h)
-#define BWD_LAUNCH_KIND(KERNEL, G, TPB_, LDS_, ...)                                                                         \
-  do {                                                                                                                        \
-    if (bf16 == POLICY_GVPDEF) {                                                                                              \
-      CGVP_SET_DYN_LDS_ONCE(KERNEL(f32_gvpdef), LDS_);                                                                        \
-      hipLaunchKernelGGL((KERNEL(f32_gvpdef)), dim3(G), dim3(TPB_), (LDS_), st, __VA_ARGS__);                                       \
-    } else if (bf16 == POLICY_LINEAR) {                                                                                       \
-      CGVP_SET_DYN_LDS_ONCE(KERNEL(f32_linear), LDS_);                                                                        \
-      hipLaunchKernelGGL((KERNEL(f32_linear)), dim3(G), dim3(TPB_), (LDS_), st, __VA_ARGS__);                                       \
-    } else {                                                                                                                  \
-      BWD_LAUNCH(KERNEL, G, TPB_, LDS_, __VA_ARGS__);                                                                         \
-    }                                                                                                                         \
-  } while (0)
-
 int node_update_bwd(const float* img_node, const float* imgT_node, const float* h, const float* dh,
                     const float* mask0, const float* mask1, gvp::RngArgs rng, const float* g_up0, const float* g_up1,
                     const float* g_up2, int64_t N, float* g_dh, float* g_h, float* zero_rows, float* slab, int* grid,
-                    int bf16, hipStream_t st) {
+                    int policy, hipStream_t st) {
   NodeBArgs a{img_node, imgT_node, h, dh, mask0, mask1, rng, g_up0, g_up1, g_up2, N, g_dh, g_h, zero_rows, slab};
-  const int G = grid_for((N + TILE - 1) / TILE);
+  const int64_t tiles = (N + TILE - 1) / TILE;
+  const int G = grid_for(tiles);
   *grid = G;
   const size_t lds = (size_t)node_bwd_lds_floats() * sizeof(float);
-  if (one_tile_per_wave((N + TILE - 1) / TILE, G)) {
-#define K_(ST) node_bwd_kernel<ST, true>
-    BWD_LAUNCH_KIND(K_, G, BW_TPB, lds, a);
-#undef K_
-    return 0;
-  }
-#define K_(ST) node_bwd_kernel<ST>
-  BWD_LAUNCH_KIND(K_, G, BW_TPB, lds, a);
-#undef K_
-  return 0;
+  return with_policy<true>(policy, [&](auto tag) {
+    using ST = typename decltype(tag)::type;
+    return with_flag(one_tile_per_wave(tiles, G), [&](auto one) {
+      return launch<node_bwd_kernel<ST, one.value>>(dim3(G), dim3(BW_TPB), lds, st, a);
+    });
+  });
 }
 
 // head + node stage of the last layer in one launch (see node_head_bwd_kernel); g_h_out must be the node stage's g_up0
 int node_head_bwd(const float* img_head, const float* imgT_head, const float* h_out, const float* g_out, float* g_h_out,
                   float* head_slab, const float* img_node, const float* imgT_node, const float* h, const float* dh,
                   const float* mask0, const float* mask1, gvp::RngArgs rng, int64_t N, float* g_dh, float* g_h,
-                  float* zero_rows, float* slab, int* grid, int bf16, hipStream_t st) {
+                  float* zero_rows, float* slab, int* grid, int policy, hipStream_t st) {
   HeadBArgs hd{img_head, imgT_head, h_out, g_out, N, g_h_out, head_slab};
   NodeBArgs a{img_node, imgT_node, h, dh, mask0, mask1, rng, g_h_out, nullptr, nullptr, N, g_dh, g_h, zero_rows, slab};
-  const int G = grid_for((N + TILE - 1) / TILE);
+  const int64_t tiles = (N + TILE - 1) / TILE;
+  const int G = grid_for(tiles);
   *grid = G;
   const int f = node_bwd_lds_floats() > head_bwd_lds_floats() ? node_bwd_lds_floats() : head_bwd_lds_floats();
   const size_t lds = (size_t)f * sizeof(float);
-  if (one_tile_per_wave((N + TILE - 1) / TILE, G)) {
-#define K_(ST) node_head_bwd_kernel<ST, true>
-    BWD_LAUNCH(K_, G, BW_TPB, lds, hd, a);
-#undef K_
-    return 0;
-  }
-#define K_(ST) node_head_bwd_kernel<ST>
-  BWD_LAUNCH(K_, G, BW_TPB, lds, hd, a);
-#undef K_
-  return 0;
+  return with_policy<false>(policy, [&](auto tag) {
+    using ST = typename decltype(tag)::type;
+    return with_flag(one_tile_per_wave(tiles, G), [&](auto one) {
+      return launch<node_head_bwd_kernel<ST, one.value>>(dim3(G), dim3(BW_TPB), lds, st, hd, a);
+    });
+  });
 }
 
 int head_bwd(const float* img_head, const float* imgT_head, const float* h_out, const float* g_out, int64_t N,
-             float* g_h_out, float* slab, int* grid, int bf16, hipStream_t st) {
+             float* g_h_out, float* slab, int* grid, int policy, hipStream_t st) {
   HeadBArgs a{img_head, imgT_head, h_out, g_out, N, g_h_out, slab};
   const int G = grid_for((N + TILE - 1) / TILE);
   *grid = G;
   const size_t lds = (size_t)head_bwd_lds_floats() * sizeof(float);
-#define K_(ST) head_bwd_kernel<ST>
-  BWD_LAUNCH(K_, G, BW_TPB, lds, a);
-#undef K_
-  return 0;
+  return with_policy<false>(policy, [&](auto tag) {
+    return launch<head_bwd_kernel<typename decltype(tag)::type>>(dim3(G), dim3(BW_TPB), lds, st, a);
+  });
 }
 
 // Which conv backward runs (CGVP_CONV_BWD in the environment, read once per process; the tests cross-check them):
@@ -1577,8 +1544,9 @@ int conv_bwd_version() {
   return v;
 }
 
-template <int NTE, int TN, int WPB_, bool STORE = false>
-int conv_bwd2_impl(ConvBArgs& a, int64_t E, int* grid, int bf16, hipStream_t st) {
+// the layer-kind policies exist for the conv kernels without an edge-type column only (NTE == 0)
+template <int NTE, int TN, int WPB_, bool STORE>
+int conv_bwd2_impl(ConvBArgs& a, int64_t E, int* grid, int policy, hipStream_t st) {
   typedef C2Shape<TN, WPB_> SH;
   const int64_t iters = (E + TN * TILE - 1) / (TN * TILE);
   const int64_t wgs = (iters + WPB_ - 1) / WPB_;
@@ -1586,39 +1554,35 @@ int conv_bwd2_impl(ConvBArgs& a, int64_t E, int* grid, int bf16, hipStream_t st)
   const int G = (int)(wgs < 1 ? 1 : (wgs > cap ? cap : wgs));
   *grid = G;
   const size_t lds = (size_t)SH::template lds_floats<NTE>() * sizeof(float);
-#define K_(ST) conv_bwd2_kernel<NTE, ST, TN, WPB_, STORE>
-  if (bf16 >= POLICY_GVPDEF) {
-    if constexpr (NTE == 0) BWD_LAUNCH_KIND(K_, G, SH::TPB, lds, a);
-    else return CGVP_ERR_UNSUPPORTED_DIMS;
-    return 0;
-  }
-  BWD_LAUNCH(K_, G, SH::TPB, lds, a);
-#undef K_
-  return 0;
+  return with_policy<NTE == 0>(policy, [&](auto tag) {
+    return launch<conv_bwd2_kernel<NTE, typename decltype(tag)::type, TN, WPB_, STORE>>(dim3(G), dim3(SH::TPB), lds, st, a);
+  });
 }
 
 template <int NTE>
-int conv_bwd_impl(ConvBArgs& a, int* grid, int bf16, hipStream_t st) {
+int conv_bwd_impl(ConvBArgs& a, int* grid, int policy, hipStream_t st) {
   const int64_t ngroups = (a.N + a.npw - 1) / a.npw;
   const int64_t wgs = (ngroups + CB_WPB - 1) / CB_WPB;
   const int cap = bwd_grid_cap(ngroups);
   const int G = (int)(wgs < 1 ? 1 : (wgs > cap ? cap : wgs));
   *grid = G;
   const size_t lds = (size_t)conv_bwd_lds_floats<NTE>() * sizeof(float);
-#define K_(ST) conv_bwd_kernel<NTE, ST>
-  if (bf16 >= POLICY_GVPDEF) {
-    if constexpr (NTE == 0) BWD_LAUNCH_KIND(K_, G, CB_TPB, lds, a);
-    else return CGVP_ERR_UNSUPPORTED_DIMS;
-    return 0;
-  }
-  BWD_LAUNCH(K_, G, CB_TPB, lds, a);
-#undef K_
-  return 0;
+  return with_policy<NTE == 0>(policy, [&](auto tag) {
+    return launch<conv_bwd_kernel<NTE, typename decltype(tag)::type>>(dim3(G), dim3(CB_TPB), lds, st, a);
+  });
+}
+
+template <int NTE>
+int conv_bwd_version_impl(ConvBArgs& a, int64_t E, int* grid, int policy, hipStream_t st) {
+  if (a.g_edge) return conv_bwd2_impl<NTE, 1, 8, true>(a, E, grid, policy, st);
+  if (conv_bwd_version() == 2) return conv_bwd2_impl<NTE, 2, 4, false>(a, E, grid, policy, st);
+  if (conv_bwd_version() == 3) return conv_bwd2_impl<NTE, 1, 8, false>(a, E, grid, policy, st);
+  return conv_bwd_impl<NTE>(a, grid, policy, st);
 }
 
 int conv_bwd(int nt_edge, const float* img, const float* imgT, const float* h, const float* e_emb,
              const int32_t* rowptr, const int32_t* esrc, const int32_t* edst, int64_t N, int64_t E, int mean,
-             const float* g_dh, float* g_src, float* g_dst, float* g_e, float* slab, int* grid, int bf16, hipStream_t st,
+             const float* g_dh, float* g_src, float* g_dst, float* g_e, float* slab, int* grid, int policy, hipStream_t st,
              float* g_edge, float* slot) {
   // targets per wave: two 16-edge tiles' worth (the forward's 32-edge passes), as in quad::conv
   int64_t deg = N > 0 ? (E + N - 1) / N : 1;
@@ -1626,84 +1590,62 @@ int conv_bwd(int nt_edge, const float* img, const float* imgT, const float* h, c
   int npw = (int)((2 * TILE - 2) / deg);
   npw = npw < 1 ? 1 : (npw > WAVE ? WAVE : npw);
   ConvBArgs a{img, imgT, h, e_emb, rowptr, esrc, edst, N, npw, mean, g_dh, g_src, g_dst, g_e, slab, g_edge, slot};
-  if (g_edge) {         // deterministic mode: the default kernel's STORE instantiation; the A/B kernels have none
-    if (conv_bwd_version() != 3 || !slot) return CGVP_ERR_NONDETERMINISTIC;
-    if (nt_edge == 0) return conv_bwd2_impl<0, 1, 8, true>(a, E, grid, bf16, st);
-    if (nt_edge == 1) return conv_bwd2_impl<1, 1, 8, true>(a, E, grid, bf16, st);
-    return CGVP_ERR_UNSUPPORTED_DIMS;
-  }
-  if (conv_bwd_version() == 2) {
-    if (nt_edge == 0) return conv_bwd2_impl<0, 2, 4>(a, E, grid, bf16, st);
-    if (nt_edge == 1) return conv_bwd2_impl<1, 2, 4>(a, E, grid, bf16, st);
-    return CGVP_ERR_UNSUPPORTED_DIMS;
-  }
-  if (conv_bwd_version() == 3) {
-    if (nt_edge == 0) return conv_bwd2_impl<0, 1, 8>(a, E, grid, bf16, st);
-    if (nt_edge == 1) return conv_bwd2_impl<1, 1, 8>(a, E, grid, bf16, st);
-    return CGVP_ERR_UNSUPPORTED_DIMS;
-  }
-  if (nt_edge == 0) return conv_bwd_impl<0>(a, grid, bf16, st);
-  if (nt_edge == 1) return conv_bwd_impl<1>(a, grid, bf16, st);
+  // deterministic mode: the default kernel's STORE instantiation; the A/B kernels have none
+  if (g_edge && (conv_bwd_version() != 3 || !slot)) return CGVP_ERR_NONDETERMINISTIC;
+  if (nt_edge == 0) return conv_bwd_version_impl<0>(a, E, grid, policy, st);
+  if (nt_edge == 1) return conv_bwd_version_impl<1>(a, E, grid, policy, st);
   return CGVP_ERR_UNSUPPORTED_DIMS;
 }
 
 template <int NTE>
-int edge_bwd_impl(EdgeBArgs& a, int* grid, int bf16, hipStream_t st) {
+int edge_bwd_impl(EdgeBArgs& a, int* grid, int policy, hipStream_t st) {
   // 66 KB of LDS and 128 VGPRs per workgroup (capped: 4-8 spilled): TWO workgroups share a CU (4 waves per SIMD), so up to 2 x 240 slab rows
   const int64_t tiles = (a.E + TILE - 1) / TILE;
   const int G = (int)(tiles < 1 ? 1 : (tiles > 2 * bwd_grid_cap((tiles + 1) / 2) ? 2 * bwd_grid_cap((tiles + 1) / 2) : tiles));
   *grid = G;
   const size_t lds = (size_t)edge_bwd_lds_floats<NTE>() * sizeof(float);
-  if (a.g_e_s) {
-#define K_(ST) edge_bwd_kernel<NTE, ST, true>
-    BWD_LAUNCH(K_, G, BW_TPB, lds, a);
-#undef K_
-    return 0;
-  }
-#define K_(ST) edge_bwd_kernel<NTE, ST>
-  BWD_LAUNCH(K_, G, BW_TPB, lds, a);
-#undef K_
-  return 0;
+  return with_policy<false>(policy, [&](auto tag) {
+    using ST = typename decltype(tag)::type;
+    return with_flag(a.g_e_s != nullptr, [&](auto dx) {
+      return launch<edge_bwd_kernel<NTE, ST, dx.value>>(dim3(G), dim3(BW_TPB), lds, st, a);
+    });
+  });
 }
 
 int edge_embed_bwd(int nt_edge, const float* img, const float* imgT, const float* e_s, const float* e_v,
                    const int64_t* etypes, const int32_t* eperm, int64_t E, const float* const* g_e, int n_g,
-                   float* g_e_s, float* g_e_v, float* slab, int* grid, int bf16, hipStream_t st) {
+                   float* g_e_s, float* g_e_v, float* slab, int* grid, int policy, hipStream_t st) {
   if (n_g < 1 || n_g > EB_MAX_LAYERS) return CGVP_ERR_BAD_ARG;
   if ((g_e_s == nullptr) != (g_e_v == nullptr)) return CGVP_ERR_BAD_ARG;
   EdgeBArgs a{img, imgT, e_s, e_v, etypes, eperm, E, {}, n_g, slab, g_e_s, g_e_v};
   for (int l = 0; l < n_g; ++l) a.g_e[l] = g_e[l];
-  if (nt_edge == 0) return edge_bwd_impl<0>(a, grid, bf16, st);
-  if (nt_edge == 1) return edge_bwd_impl<1>(a, grid, bf16, st);
+  if (nt_edge == 0) return edge_bwd_impl<0>(a, grid, policy, st);
+  if (nt_edge == 1) return edge_bwd_impl<1>(a, grid, policy, st);
   return CGVP_ERR_UNSUPPORTED_DIMS;
 }
 
 template <int NTN>
-int embed_bwd_impl(EmbBArgs& a, int* grid, int bf16, hipStream_t st) {
-  const int G = grid_for((a.N + TILE - 1) / TILE);
+int embed_bwd_impl(EmbBArgs& a, int* grid, int policy, hipStream_t st) {
+  const int64_t tiles = (a.N + TILE - 1) / TILE;
+  const int G = grid_for(tiles);
   *grid = G;
   const size_t lds = (size_t)embed_bwd_lds_floats<NTN>() * sizeof(float);
-  if (one_tile_per_wave((a.N + TILE - 1) / TILE, G)) {
-#define K_(ST) embed_bwd_kernel<NTN, ST, true>
-    BWD_LAUNCH(K_, G, BW_TPB, lds, a);
-#undef K_
-    return 0;
-  }
-#define K_(ST) embed_bwd_kernel<NTN, ST>
-  BWD_LAUNCH(K_, G, BW_TPB, lds, a);
-#undef K_
-  return 0;
+  return with_policy<false>(policy, [&](auto tag) {
+    using ST = typename decltype(tag)::type;
+    return with_flag(one_tile_per_wave(tiles, G), [&](auto one) {
+      return launch<embed_bwd_kernel<NTN, ST, one.value>>(dim3(G), dim3(BW_TPB), lds, st, a);
+    });
+  });
 }
 
 int node_embed_bwd(int nt_node, const float* img, const float* imgT, const float* x_s, const float* x_v,
                    const int64_t* ntypes, int64_t N, const float* g_up0, const float* g_up1, const float* g_up2,
-                   float* g_x_s, float* g_x_v, float* slab, int* grid, int bf16, hipStream_t st) {
+                   float* g_x_s, float* g_x_v, float* slab, int* grid, int policy, hipStream_t st) {
   EmbBArgs a{img, imgT, x_s, x_v, ntypes, N, g_up0, g_up1, g_up2, g_x_s, g_x_v, slab};
-  if (nt_node == 0) return embed_bwd_impl<0>(a, grid, bf16, st);
-  if (nt_node == 20) return embed_bwd_impl<20>(a, grid, bf16, st);
-  if (nt_node == 21) return embed_bwd_impl<21>(a, grid, bf16, st);
+  if (nt_node == 0) return embed_bwd_impl<0>(a, grid, policy, st);
+  if (nt_node == 20) return embed_bwd_impl<20>(a, grid, policy, st);
+  if (nt_node == 21) return embed_bwd_impl<21>(a, grid, policy, st);
   return CGVP_ERR_UNSUPPORTED_DIMS;
 }
-
 
 }  // namespace quad

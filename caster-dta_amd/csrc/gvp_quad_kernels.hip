@@ -694,13 +694,17 @@ void offsets_impl(int num_convs, QuadOffsets* o) {
   o->layerT_stride = IM::TC_SIZE + IM::TN_SIZE; o->headT = IM::headT(num_convs);
 }
 
-#define DISPATCH_NT(NTN_, NTE_, CALL)                       \
-  if (NTN_ == 0 && NTE_ == 0) { CALL(0, 0); }               \
-  else if (NTN_ == 20 && NTE_ == 1) { CALL(20, 1); }        \
-  else if (NTN_ == 21 && NTE_ == 1) { CALL(21, 1); }        \
-  else if (NTN_ == 20 && NTE_ == 0) { CALL(20, 0); }        \
-  else if (NTN_ == 0 && NTE_ == 1) { CALL(0, 1); }          \
-  else return CGVP_ERR_UNSUPPORTED_DIMS;
+// `f(ntn, nte)` with the one-hot widths of the compiled encoder shapes as std::integral_constant tags
+template <int V> using Int = std::integral_constant<int, V>;
+template <class F>
+int with_nt(int ntn, int nte, F&& f) {
+  if (ntn == 0 && nte == 0) return f(Int<0>{}, Int<0>{});
+  if (ntn == 20 && nte == 1) return f(Int<20>{}, Int<1>{});
+  if (ntn == 21 && nte == 1) return f(Int<21>{}, Int<1>{});
+  if (ntn == 20 && nte == 0) return f(Int<20>{}, Int<0>{});
+  if (ntn == 0 && nte == 1) return f(Int<0>{}, Int<1>{});
+  return CGVP_ERR_UNSUPPORTED_DIMS;
+}
 
 }  // namespace
 
@@ -713,57 +717,54 @@ extern "C" int cgvp_debug_set_stamp_buffer(unsigned long long* buf) {
 #endif
 
 int offsets(int nt_node, int nt_edge, int num_convs, QuadOffsets* o) {
-#define CALL(A, B) offsets_impl<A, B>(num_convs, o)
-  DISPATCH_NT(nt_node, nt_edge, CALL)
-#undef CALL
-  return 0;
+  return with_nt(nt_node, nt_edge, [&](auto ntn, auto nte) {
+    offsets_impl<decltype(ntn)::value, decltype(nte)::value>(num_convs, o);
+    return 0;
+  });
 }
 
 int prepare(const EncLayout& L, int num_convs, int packed, const float* params, float* image, hipStream_t st) {
-#define CALL(A, B) prepare_impl<A, B>(L, num_convs, packed, params, image, st)
-  DISPATCH_NT(L.nt_node, L.nt_edge, CALL)
-#undef CALL
-  return 0;
+  return with_nt(L.nt_node, L.nt_edge, [&](auto ntn, auto nte) {
+    return prepare_impl<decltype(ntn)::value, decltype(nte)::value>(L, num_convs, packed, params, image, st);
+  });
 }
 
 int node_embed(int nt_node, const float* img, const float* x_s, const float* x_v, const int64_t* ntypes,
-               int64_t N, float* h, unsigned long long* rng_state, unsigned long long* rng_out, int bf16, hipStream_t st) {
+               int64_t N, float* h, unsigned long long* rng_state, unsigned long long* rng_out, int policy, hipStream_t st) {
   EmbedQArgs a{img, x_s, x_v, ntypes, N, h, rng_state, rng_out};
   const dim3 grid((unsigned)((N + WPB * TILE - 1) / (WPB * TILE)));
-#define EMB_LAUNCH(NT) { if (bf16) hipLaunchKernelGGL((embed_quad_kernel<NT, bf16s>), grid, dim3(TPB), 0, st, a); \
-                         else hipLaunchKernelGGL((embed_quad_kernel<NT, float>), grid, dim3(TPB), 0, st, a); }
-  switch (nt_node) {
-    case 0: EMB_LAUNCH(0) break;
-    case 20: EMB_LAUNCH(20) break;
-    case 21: EMB_LAUNCH(21) break;
-    default: return CGVP_ERR_UNSUPPORTED_DIMS;
-  }
-#undef EMB_LAUNCH
-  return 0;
+  return with_policy<false>(policy, [&](auto tag) {
+    using ST = typename decltype(tag)::type;
+    switch (nt_node) {
+      case 0: return launch<embed_quad_kernel<0, ST>>(grid, dim3(TPB), 0, st, a);
+      case 20: return launch<embed_quad_kernel<20, ST>>(grid, dim3(TPB), 0, st, a);
+      case 21: return launch<embed_quad_kernel<21, ST>>(grid, dim3(TPB), 0, st, a);
+      default: return CGVP_ERR_UNSUPPORTED_DIMS;
+    }
+  });
 }
 
 template <int NTN, int NTE>
-int pass_begin_impl(const PassBeginArgs& a, int blocks, int bf16, hipStream_t st) {
-  if (bf16) hipLaunchKernelGGL((pass_begin_kernel<NTN, NTE, bf16s>), dim3(blocks), dim3(TPB), 0, st, a);
-  else hipLaunchKernelGGL((pass_begin_kernel<NTN, NTE, float>), dim3(blocks), dim3(TPB), 0, st, a);
-  return 0;
+int pass_begin_impl(const PassBeginArgs& a, int blocks, int policy, hipStream_t st) {
+  return with_policy<false>(policy, [&](auto tag) {
+    return launch<pass_begin_kernel<NTN, NTE, typename decltype(tag)::type>>(dim3(blocks), dim3(TPB), 0, st, a);
+  });
 }
-int pass_begin(const EncLayout& L, int num_convs, int bf16, const float* params, float* image, const float* x_s,
+int pass_begin(const EncLayout& L, int num_convs, int policy, const float* params, float* image, const float* x_s,
                const float* x_v, const int64_t* ntypes, int64_t N, float* h, unsigned long long* rng_state,
                unsigned long long* rng_out, const int64_t* edge_index, int64_t E, int32_t* counters, hipStream_t st) {
   QuadOffsets o;
   if (int rc = offsets(L.nt_node, L.nt_edge, num_convs, &o)) return rc;
   PassBeginArgs a{};
   a.e = EmbedQArgs{nullptr, x_s, x_v, ntypes, N, h, rng_state, rng_out};
-  a.params = params; a.L = L; a.num_convs = num_convs; a.packed = bf16 ? 1 : 0; a.image = image;
+  a.params = params; a.L = L; a.num_convs = num_convs; a.packed = policy == POLICY_BF16 ? 1 : 0; a.image = image;
   a.ei = edge_index; a.E = (edge_index && counters) ? E : 0; a.Ncount = N; a.counters = counters;
   a.embed_blocks = (int)((N + WPB * TILE - 1) / (WPB * TILE));
   a.prep_blocks = (o.total + TPB - 1) / TPB;
   const int blocks = a.embed_blocks + a.prep_blocks + (int)((a.E + TPB - 1) / TPB);
-#define CALL(A, B) pass_begin_impl<A, B>(a, blocks, bf16, st)
-  DISPATCH_NT(L.nt_node, L.nt_edge, CALL)
-#undef CALL
-  return 0;
+  return with_nt(L.nt_node, L.nt_edge, [&](auto ntn, auto nte) {
+    return pass_begin_impl<decltype(ntn)::value, decltype(nte)::value>(a, blocks, policy, st);
+  });
 }
 
 // 8-wave workgroups only while they all fit one-per-CU in a single round (their 100 KB of LDS allows no second
@@ -778,9 +779,7 @@ template <int NTE, int FUSE, int EMODE, typename ST, int CW>
 int conv_launch_w(const ConvQArgs& a, int64_t groups, hipStream_t st) {
   const size_t lds = (size_t)(Image<0, NTE>::CV_SIZE + (FUSE == 0 ? 0 : Image<0, 0>::ND_SIZE + (FUSE == 2 ? Image<0, 0>::HD_SIZE : 0)) +
                               CW * WAVE * ROW) * sizeof(float);
-  if (lds > 64 * 1024) CGVP_SET_DYN_LDS_ONCE((conv_quad_kernel<NTE, FUSE, EMODE, ST, CW>), lds);      // once per kernel and device; an error is returned
-  hipLaunchKernelGGL((conv_quad_kernel<NTE, FUSE, EMODE, ST, CW>), dim3((unsigned)((groups + CW - 1) / CW)), dim3(WAVE * CW), lds, st, a);
-  return 0;
+  return launch<conv_quad_kernel<NTE, FUSE, EMODE, ST, CW>>(dim3((unsigned)((groups + CW - 1) / CW)), dim3(WAVE * CW), lds, st, a);
 }
 template <int NTE, int FUSE, int EMODE, typename ST>
 int conv_launch_e(const ConvQArgs& a, int64_t groups, hipStream_t st) {
@@ -793,19 +792,15 @@ int conv_launch_s(const ConvQArgs& a, int64_t grid, hipStream_t st) {
   if (a.e_out) return conv_launch_e<NTE, FUSE, 1, ST>(a, grid, st);
   return conv_launch_e<NTE, FUSE, 0, ST>(a, grid, st);
 }
-// `bf16` below is the tile policy index (gvp_internal.h, POLICY_*): 0 float, 1 bf16s, 2 f32_gvpdef, 3 f32_linear
 template <int NTE, int FUSE>
-int conv_launch(const ConvQArgs& a, int64_t grid, int bf16, hipStream_t st) {
-  if (bf16 >= POLICY_GVPDEF) {      // the other layer kinds: stand-alone layers (stored edge embedding, no type columns, two launches)
-    if constexpr (NTE == 0 && FUSE == 0) {
-      if (!a.e_in) return CGVP_ERR_UNSUPPORTED_DIMS;
-      if (bf16 == POLICY_GVPDEF) return conv_launch_e<0, 0, 2, f32_gvpdef>(a, grid, st);
-      return conv_launch_e<0, 0, 2, f32_linear>(a, grid, st);
-    }
-    return CGVP_ERR_UNSUPPORTED_DIMS;
-  }
-  if (bf16) return conv_launch_s<NTE, FUSE, bf16s>(a, grid, st);
-  return conv_launch_s<NTE, FUSE, float>(a, grid, st);
+int conv_launch(const ConvQArgs& a, int64_t grid, int policy, hipStream_t st) {
+  return with_policy<NTE == 0 && FUSE == 0>(policy, [&](auto tag) {
+    using ST = typename decltype(tag)::type;
+    if constexpr (is_layer_kind<ST>)      // the other layer kinds: stand-alone layers (stored edge embedding, no type columns, two launches)
+      return a.e_in ? conv_launch_e<NTE, FUSE, 2, ST>(a, grid, st) : CGVP_ERR_UNSUPPORTED_DIMS;
+    else
+      return conv_launch_s<NTE, FUSE, ST>(a, grid, st);
+  });
 }
 
 // fuse: 0 = conv only (dh required); 1 / 2 = the layer's node update (2: with the output head) in the same launch
@@ -813,7 +808,7 @@ int conv(int nt_edge, const float* img, const float* h, const float* e_s, const 
          const int64_t* etypes, const int32_t* rowptr, const int32_t* eperm, const int32_t* esrc,
          const int32_t* edst, int64_t N, int64_t E, int mean, float* dh, int fuse, const float* img_node,
          const float* img_head, float* h_out, float* out, const float* mask0, const float* mask1, gvp::RngArgs rng,
-         const float* e_in, float* e_out, int bf16, hipStream_t st) {
+         const float* e_in, float* e_out, int policy, hipStream_t st) {
   // target nodes per wave: one pass of CTN lockstep 16-edge tiles (~30 edges) per wave
   int64_t deg = N > 0 ? (E + N - 1) / N : 1;
   if (deg < 1) deg = 1;
@@ -837,32 +832,28 @@ int conv(int nt_edge, const float* img, const float* h, const float* e_s, const 
   if (nt_edge != 0 && nt_edge != 1) return CGVP_ERR_UNSUPPORTED_DIMS;
   if (fuse < 0 || fuse > 2) return CGVP_ERR_BAD_ARG;
   if (nt_edge == 0) {
-    if (fuse == 0) return conv_launch<0, 0>(a, grid, bf16, st);
-    if (fuse == 1) return conv_launch<0, 1>(a, grid, bf16, st);
-    return conv_launch<0, 2>(a, grid, bf16, st);
+    if (fuse == 0) return conv_launch<0, 0>(a, grid, policy, st);
+    if (fuse == 1) return conv_launch<0, 1>(a, grid, policy, st);
+    return conv_launch<0, 2>(a, grid, policy, st);
   }
-  if (fuse == 0) return conv_launch<1, 0>(a, grid, bf16, st);
-  if (fuse == 1) return conv_launch<1, 1>(a, grid, bf16, st);
-  return conv_launch<1, 2>(a, grid, bf16, st);
+  if (fuse == 0) return conv_launch<1, 0>(a, grid, policy, st);
+  if (fuse == 1) return conv_launch<1, 1>(a, grid, policy, st);
+  return conv_launch<1, 2>(a, grid, policy, st);
 }
 
 int node_update(const float* img_node, const float* img_head, const float* h, const float* dh, int64_t N,
                 int with_head, float* h_out, float* out, const float* mask0, const float* mask1, gvp::RngArgs rng,
-                int bf16, hipStream_t st) {
+                int policy, hipStream_t st) {
   NodeQArgs a{img_node, img_head, h, dh, N, h_out, out, mask0, mask1, rng};
   const dim3 grid((unsigned)((N + WPB * TILE - 1) / (WPB * TILE)));
-  if (bf16 >= POLICY_GVPDEF) {
-    if (with_head) return CGVP_ERR_UNSUPPORTED_DIMS;
-    if (bf16 == POLICY_GVPDEF) hipLaunchKernelGGL((node_quad_kernel<false, f32_gvpdef>), grid, dim3(TPB), 0, st, a);
-    else hipLaunchKernelGGL((node_quad_kernel<false, f32_linear>), grid, dim3(TPB), 0, st, a);
-  } else if (bf16) {
-    if (with_head) hipLaunchKernelGGL((node_quad_kernel<true, bf16s>), grid, dim3(TPB), 0, st, a);
-    else hipLaunchKernelGGL((node_quad_kernel<false, bf16s>), grid, dim3(TPB), 0, st, a);
-  } else {
-    if (with_head) hipLaunchKernelGGL((node_quad_kernel<true, float>), grid, dim3(TPB), 0, st, a);
-    else hipLaunchKernelGGL((node_quad_kernel<false, float>), grid, dim3(TPB), 0, st, a);
-  }
-  return 0;
+  return with_policy<true>(policy, [&](auto tag) {
+    using ST = typename decltype(tag)::type;
+    return with_flag(with_head != 0, [&](auto head) {
+      constexpr bool HEAD = decltype(head)::value;
+      if constexpr (HEAD && is_layer_kind<ST>) return CGVP_ERR_UNSUPPORTED_DIMS;      // the head is CASTER-DTA's
+      else return launch<node_quad_kernel<HEAD, ST>>(grid, dim3(TPB), 0, st, a);
+    });
+  });
 }
 
 }  // namespace quad

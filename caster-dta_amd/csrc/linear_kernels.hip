@@ -131,6 +131,15 @@ int splits_for(int64_t R, int O) {
   return (int)(s < 1 ? 1 : s);
 }
 
+// The dynamic-LDS attribute is set ONCE per instantiation and device, so it must cover the LARGEST I that instantiation
+// serves (I <= IMAX = 80 / 144 / 256 for NTW = 3 / 5 / 9), not the I of whichever call happened to come first.
+template <int NTW, int IMAX>
+int launch_wgrad(dim3 grid, size_t lds, hipStream_t st, const WgArgs& a) {
+  constexpr size_t lds_max = (size_t)(KC * (IMAX + 16) + KC * (OG + 16)) * sizeof(float);
+  static_assert((IMAX / 16 + 2) / 2 <= NTW && lds_max <= 160 * 1024, "instantiation bound");
+  return launch_reserving<linear_wgrad_kernel<NTW>>(grid, dim3(TPB), lds, lds_max, st, a);
+}
+
 }  // namespace
 
 extern "C" {
@@ -159,17 +168,8 @@ int cgvp_linear_wgrad(const float* x, const float* gy, int64_t R, int32_t I, int
   const dim3 grid((unsigned)((R + rps - 1) / rps), (unsigned)(O / OG));
   const size_t lds = (size_t)(KC * (I + 16) + KC * (OG + 16)) * sizeof(float);
   const int ntw = (I / 16 + 1 + 1) / 2;                    // column tiles of the busier parity
-  // The dynamic-LDS attribute is set ONCE per instantiation and device, so it must cover the LARGEST I that instantiation
-  // serves (I <= 80 / 144 / 256 for N_ = 3 / 5 / 9), not the I of whichever call happened to come first.
-#define LAUNCH(N_, IMAX_)                                                                                       \
-  do {                                                                                                          \
-    constexpr size_t lds_max_ = (size_t)(KC * ((IMAX_) + 16) + KC * (OG + 16)) * sizeof(float);                  \
-    static_assert(((IMAX_) / 16 + 2) / 2 <= (N_) && lds_max_ <= 160 * 1024, "instantiation bound");             \
-    CGVP_SET_DYN_LDS_ONCE(linear_wgrad_kernel<N_>, lds_max_);                                                   \
-    hipLaunchKernelGGL(linear_wgrad_kernel<N_>, grid, dim3(TPB), lds, st, a);                                   \
-  } while (0)
-  if (ntw <= 3) LAUNCH(3, 80); else if (ntw <= 5) LAUNCH(5, 144); else LAUNCH(9, 256);
-#undef LAUNCH
+  if (int rc = ntw <= 3 ? launch_wgrad<3, 80>(grid, lds, st, a)
+             : ntw <= 5 ? launch_wgrad<5, 144>(grid, lds, st, a) : launch_wgrad<9, 256>(grid, lds, st, a)) return rc;
   cgvp_segment sg[2] = {{workspace, (int)grid.x, len, 0, O * I, 0}, {workspace, (int)grid.x, len, O * I, O, O * I}};
   quad::reduce_segments(sg, 2, out, st, 1);
   const hipError_t e = hipGetLastError();
