@@ -9,6 +9,7 @@ mkdir -p "$OUT" "$TMP"
 SRCS=(gvp_kernels gvp_quad_kernels gvp_quad_bwd_kernels gine_quad_kernels pass_api)
 [ -f "$HERE/attn_kernels.hip" ] && SRCS+=(attn_kernels)
 [ -f "$HERE/feat_kernels.hip" ] && SRCS+=(feat_kernels)
+[ -f "$HERE/structure_kernels.hip" ] && SRCS+=(structure_kernels)
 [ -f "$HERE/linear_kernels.hip" ] && SRCS+=(linear_kernels)
 [ -f "$HERE/norm_kernels.hip" ] && SRCS+=(norm_kernels)
 [ -f "$HERE/elementwise_kernels.hip" ] && SRCS+=(elementwise_kernels)

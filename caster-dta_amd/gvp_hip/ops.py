@@ -312,6 +312,9 @@ def edge_features(ca_xyz, seq_index, edge_index):
     return e_s, e_v
 
 
+from .structure import protein_graphs  # noqa: E402,F401  (backbone atoms -> the whole graph dict: builds the edge list too)
+
+
 def prepare_image(params, layout, dims):
     """Fragment image of the arena for the MFMA kernels (one small launch)."""
     L = _lib.lib()
