@@ -339,7 +339,8 @@ __global__ __launch_bounds__(TPB) void attn_bwd_dkv_kernel(Args a) {
 
 // ------------------------------------------------------------------------------------------------ head-averaged weights
 // nn.MultiheadAttention(need_weights=True, average_attn_weights=True): w[b][q][k] = mean_h P_h[q][k], written straight
-// into the reference's dense layout [B][w_lq][w_lk] (zero elsewhere; the caller zero-fills).  Inference only
+// into the reference's dense layout [B][w_lq][w_lk] (zero elsewhere; the caller zero-fills; a pair with more than
+// w_lq queries or w_lk keys is truncated to the layout, nothing is written outside it).  Inference only
 // (inference/evaluation.py:43-66 slices it per pair); one wave per 16-query tile, all heads.
 __global__ __launch_bounds__(TPB) void attn_weights_kernel(Args a) {
   const int lane = threadIdx.x & 63, n = lane & 15, g = lane >> 4;
@@ -355,9 +356,11 @@ __global__ __launch_bounds__(TPB) void attn_weights_kernel(Args a) {
   const int64_t k0 = P.k_ptr[b], k_end = P.k_ptr[b + 1], qbase = P.q_ptr[b];
   const int64_t qr = q0 + n;
   const bool qv = qr < q_end;
+  const bool qw = qv && qr - qbase < P.w_lq;                     // a pair longer than the layout is truncated, never
+  const int64_t k_stop = k_end < k0 + P.w_lk ? k_end : k0 + P.w_lk;   // written past [w_lq][w_lk]
   const int E = a.E;
   const float invh = 1.0f / (float)a.H;
-  for (int64_t kb = k0; kb < k_end; kb += TILE) {
+  for (int64_t kb = k0; kb < k_stop; kb += TILE) {
     const int64_t kr = kb + n;
     f4 w = {0.f, 0.f, 0.f, 0.f};
     for (int h = 0; h < a.H; ++h) {
@@ -372,11 +375,11 @@ __global__ __launch_bounds__(TPB) void attn_weights_kernel(Args a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) w[r] += (qv && kb + 4 * g + r < k_end) ? fexp(st[r] - lse) * invh : 0.f;
     }
-    if (qv) {
+    if (qw) {
       float* row = P.w + ((int64_t)b * P.w_lq + (qr - qbase)) * P.w_lk + (kb - k0) + 4 * g;
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        if (kb + 4 * g + r < k_end) row[r] = w[r];
+        if (kb + 4 * g + r < k_stop) row[r] = w[r];
     }
   }
 }

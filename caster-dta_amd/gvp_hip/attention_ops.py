@@ -138,7 +138,8 @@ torch.library.register_autocast("caster_gvp::cross_attention", "cuda", torch.flo
 def cross_attention_weights_op(q_r: Tensor, k_a: Tensor, lse_r: Tensor, q_a: Tensor, k_r: Tensor, lse_a: Tensor,
                                rptr: Tensor, aptr: Tensor, heads: int, r_max: int,
                                a_max: int) -> Tuple[Tensor, Tensor]:
-    """-> (w_r [B, r_max, a_max], w_a [B, a_max, r_max]): head-averaged attention weights, zero in the padding."""
+    """-> (w_r [B, r_max, a_max], w_a [B, a_max, r_max]): head-averaged attention weights, zero in the padding.
+    A pair with more than r_max residues or a_max atoms is truncated to the layout (its kept entries unchanged)."""
     ts = [_f32(t, "attention operand") for t in (q_r, k_a, k_a, q_a, k_r, k_r)]
     lse_r, lse_a = _f32(lse_r, "lse"), _f32(lse_a, "lse")
     rptr, aptr = _i64c(rptr, "rptr"), _i64c(aptr, "aptr")
@@ -146,6 +147,8 @@ def cross_attention_weights_op(q_r: Tensor, k_a: Tensor, lse_r: Tensor, q_a: Ten
     B = int(rptr.numel()) - 1
     w_r = torch.zeros(B, r_max, a_max, dtype=torch.float32, device=dev)
     w_a = torch.zeros(B, a_max, r_max, dtype=torch.float32, device=dev)
+    if w_r.numel() == 0:                                     # no pair, or one side empty in every pair: nothing to write
+        return w_r, w_a
     dummy_r, dummy_a = torch.empty(1, device=dev), torch.empty(1, device=dev)    # `out` is not written by this entry point
     P = _problems(*ts, rptr, aptr)
     v = lambda t: _ptr(t).value or 0

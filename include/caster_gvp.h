@@ -443,7 +443,10 @@ int cgvp_attn_bwd(const cgvp_attn_problem* problems, int32_t num_problems, int64
                   float scale, void* stream);
 /* nn.MultiheadAttention's returned weights (need_weights=True, averaged over heads) in the reference's dense
  * layout [num_pairs][weights_lq][weights_lk] (what inference/evaluation.py:43-66 slices per pair); needs the lse
- * of cgvp_attn_fwd.  Inference only. */
+ * of cgvp_attn_fwd.  weights_lq / weights_lk are normally the longest pair's query / key count; a pair with more
+ * queries than weights_lq or more keys than weights_lk is TRUNCATED to its first weights_lq x weights_lk entries
+ * (the kept entries are unchanged: rows then sum to less than 1) and nothing is written outside the layout.
+ * Inference only. */
 int cgvp_attn_weights(const cgvp_attn_problem* problems, int32_t num_problems, int64_t num_pairs, int32_t heads,
                       float scale, void* stream);
 
