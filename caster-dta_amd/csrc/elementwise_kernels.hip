@@ -80,6 +80,8 @@ gvp::RngArgs args_of(const cgvp_rng* rng) {
   if (!rng || !rng->seed || rng->p <= 0.f) return gvp::RngArgs{nullptr, 0.f, 0};
   return gvp::RngArgs{reinterpret_cast<const unsigned long long*>(rng->seed), rng->p, rng->stream};
 }
+// The backward reads act' off the sign of the saved OUTPUT (y > 0 ? 1 : slope), which is the sign of t only for slope >= 0.
+bool slope_ok(float slope) { return slope >= 0.f && slope <= 3.402823466e38f; }
 template <int MODE>
 int launch(const float* a, const float* b, const cgvp_rng* rng, float slope, int64_t rows, int32_t dim, float* out, void* stream) {
   if (rows == 0) return 0;
@@ -109,6 +111,7 @@ int cgvp_dropout_scale(const float* g, const cgvp_rng* rng, int64_t rows, int32_
 
 int cgvp_act_dropout_fwd(const float* t, const cgvp_rng* rng, float slope, int64_t rows, int32_t dim, float* y, void* stream) {
   if (int rc = check(t, rng, rows, dim, y)) return rc;
+  if (!slope_ok(slope)) return CGVP_ERR_BAD_ARG;
   return launch<2>(t, nullptr, rng, slope, rows, dim, y, stream);
 }
 
@@ -116,6 +119,7 @@ int cgvp_act_dropout_bwd(const float* g, const float* y, const cgvp_rng* rng, fl
                          void* stream) {
   if (int rc = check(g, rng, rows, dim, gt)) return rc;
   if (rows > 0 && (!y || ((uintptr_t)y & 15))) return CGVP_ERR_BAD_ARG;
+  if (!slope_ok(slope)) return CGVP_ERR_BAD_ARG;
   return launch<3>(g, y, rng, slope, rows, dim, gt, stream);
 }
 

@@ -354,5 +354,7 @@ def _slope(activation):
     if isinstance(activation, torch.nn.ReLU) or activation is torch.relu or activation is torch.nn.functional.relu:
         return 0.0
     if isinstance(activation, torch.nn.LeakyReLU):
-        return float(activation.negative_slope)
+        slope = float(activation.negative_slope)
+        # the backward takes act' from the sign of the saved output: only a finite slope >= 0 keeps the sign of t
+        return slope if 0.0 <= slope < float("inf") else None
     return None

@@ -629,7 +629,8 @@ int cgvp_layer_norm_bwd(const float* gy, const float* x, const float* mean, cons
  *   cgvp_act_dropout_fwd  y = LeakyReLU_slope(t) * f  (slope 0: ReLU)    activation + nn.Dropout
  *   cgvp_act_dropout_bwd  gt = g * f * (y > 0 ? 1 : slope)               from the saved OUTPUT y
  * f = inverted-dropout factor of (row, column) regenerated from `rng` ({seed, offset} pair on the device, p, stream id =
- * the call site; rng NULL or p = 0: f = 1); same generator as the encoders' in-kernel dropout (cgvp_rng above). */
+ * the call site; rng NULL or p = 0: f = 1); same generator as the encoders' in-kernel dropout (cgvp_rng above).
+ * slope must be finite and >= 0 (the sign of y is then the sign of t); anything else: CGVP_ERR_BAD_ARG. */
 int cgvp_dropout_add(const float* a, const float* x, const cgvp_rng* rng, int64_t rows, int32_t dim, float* y, void* stream);
 int cgvp_dropout_scale(const float* g, const cgvp_rng* rng, int64_t rows, int32_t dim, float* out, void* stream);
 int cgvp_act_dropout_fwd(const float* t, const cgvp_rng* rng, float slope, int64_t rows, int32_t dim, float* y, void* stream);
