@@ -35,7 +35,8 @@ def _csr_numpy(ei, n):
 
 @pytest.mark.parametrize("case", ["davis", "knn", "ragged", "empty_edges", "isolated", "crowded", "large"])
 def test_csr_from_coo(case):
-    """Tables of fewer than 64k targets take the multi-workgroup scan; "large" (70k targets) the one-block tile scan."""
+    """Tables of at most 65,535 targets (N + 1 <= 65,536 row pointers) take the multi-workgroup scan; "large" (70k
+    targets) the one-block tile scan."""
     if case == "davis":
         gb = ds.protein_batch(4, 3)
     elif case == "knn":
