@@ -210,13 +210,20 @@ class GraphedTrainStep(_BucketedGraphs):
             loss, pred = step.run(pdata, mdata, y)                           # p.grad of every parameter is set
             optimizer.step()
 
+    With `optimizer=` a gvp_hip.optim.FusedAdam over `model.parameters()`, the update (unscale, clip, Adam, and the
+    scaler's update when `scaler` is given: train_model.py:578-587) is part of the captured step: `run` still returns
+    (loss, pred) and publishes p.grad, and the caller calls neither `optimizer.step()` nor `scaler.update()`.  The optimizer
+    state is shared by all buckets, only the gradient addresses are per bucket; the warm-up passes of a capture run the
+    update dry.  The learning rate is read from `param_groups[0]["lr"]` at every `run`; the other hyperparameters are those
+    of the construction.  Not together with `enable_pair_parallel` (the all-reduce sits between backward and update).
+
     One launch stages the batch into the bucket's padded static buffers, one replay runs the step.  Padding: padded
     residues / atoms are isolated nodes that belong to an extra (B+1)-th pair whose prediction the loss never reads, so
     every real pair's numbers and every gradient equal those of the eager step on the unpadded batch (padded rows have
     zero upstream gradient; tests/test_hip_models.py::test_graphed_train_step_equals_eager).  The gradients are the graph's
     static tensors: consume them (optimizer step) before the next `run` of the same bucket."""
 
-    def __init__(self, model, loss_fn, scaler=None, autocast=None, quantum=bucket_size):
+    def __init__(self, model, loss_fn, scaler=None, autocast=None, quantum=bucket_size, optimizer=None):
         if _lib.bridge() is None:
             # the capture-safety check below (_check_no_foreign_graph) lives in the C++ bridge: without it a forgotten eager
             # `loss` / `pred` turns the next capture into a segmentation fault inside hipStreamEndCapture
@@ -228,6 +235,23 @@ class GraphedTrainStep(_BucketedGraphs):
         self.buckets = {}
         self.stream = torch.cuda.Stream(device=self.device)          # capture + replay stream
         self.pool = None
+        self.optimizer = optimizer
+        if optimizer is not None:
+            from .optim import FusedAdam
+            if not isinstance(optimizer, FusedAdam):
+                raise TypeError(f"GraphedTrainStep(optimizer=...) captures a gvp_hip.optim.FusedAdam, not a {type(optimizer).__name__}: "
+                                "step any other optimizer after `run`, from the published p.grad")
+            self._check_not_pair_parallel()
+            slot = {id(p): i for i, p in enumerate(optimizer.param_groups[0]["params"])}
+            if any(id(p) not in slot for p in self.params):
+                raise ValueError("GraphedTrainStep(optimizer=...): the optimizer must hold every trainable parameter of the model "
+                                 "(FusedAdam(model.parameters(), ...))")
+            self._opt_slots, self._opt_key = [slot[id(p)] for p in self.params], optimizer.hyper_key()
+
+    def _check_not_pair_parallel(self):
+        if getattr(self.model, "_pair_parallel", False):
+            raise RuntimeError("GraphedTrainStep(optimizer=...) cannot be combined with enable_pair_parallel(): the gradient "
+                               "all-reduce belongs between the backward pass and the update")
 
     def _new_bucket(self, key, sdt, pdata, mdata, target):
         N, E, Na, Ea, B = key
@@ -270,6 +294,13 @@ class GraphedTrainStep(_BucketedGraphs):
                 self.model.attention_weights = aw
         out = self.scaler.scale(loss) if self.scaler is not None else loss
         grads = torch.autograd.grad(out, self.params, allow_unused=True)
+        if self.optimizer is not None:
+            # the update on the captured gradients; the two warm-up passes of a capture (_replay) only compute the norm,
+            # otherwise the first batch of every bucket would be applied three times
+            full = [None] * len(self.optimizer.param_groups[0]["params"])
+            for i, g in zip(self._opt_slots, grads):
+                full[i] = g
+            self.optimizer.apply(full, scaler=self.scaler, dry=not torch.cuda.is_current_stream_capturing())
         return loss.detach(), pred[:B].detach(), grads
 
     @staticmethod
@@ -293,4 +324,10 @@ class GraphedTrainStep(_BucketedGraphs):
         Na, Ea = mdata["x"].shape[0], mdata["edge_index"].shape[1]
         B = int(pdata["ptr"].numel()) - 1
         key = (self.quantum(N + 1), self.quantum(E), self.quantum(Na + 1), self.quantum(Ea), B)
+        if self.optimizer is not None:
+            self._check_not_pair_parallel()
+            if self.optimizer.hyper_key() != self._opt_key:
+                raise RuntimeError("the optimizer's betas / eps / weight decay / max_grad_norm changed since GraphedTrainStep was "
+                                   "built: captured steps keep the old values (only the learning rate is read at run time)")
+            self.optimizer.sync_lr()
         return self._publish(self._replay(key, pdata, mdata, target))
