@@ -11,6 +11,7 @@ SRCS=(gvp_kernels gvp_quad_kernels gvp_quad_bwd_kernels gine_quad_kernels pass_a
 [ -f "$HERE/feat_kernels.hip" ] && SRCS+=(feat_kernels)
 [ -f "$HERE/structure_kernels.hip" ] && SRCS+=(structure_kernels)
 [ -f "$HERE/optim_kernels.hip" ] && SRCS+=(optim_kernels)
+[ -f "$HERE/metrics_kernels.hip" ] && SRCS+=(metrics_kernels)
 [ -f "$HERE/linear_kernels.hip" ] && SRCS+=(linear_kernels)
 [ -f "$HERE/norm_kernels.hip" ] && SRCS+=(norm_kernels)
 [ -f "$HERE/elementwise_kernels.hip" ] && SRCS+=(elementwise_kernels)

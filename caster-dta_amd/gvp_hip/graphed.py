@@ -217,13 +217,17 @@ class GraphedTrainStep(_BucketedGraphs):
     update dry.  The learning rate is read from `param_groups[0]["lr"]` at every `run`; the other hyperparameters are those
     of the construction.  Not together with `enable_pair_parallel` (the all-reduce sits between backward and update).
 
+    With `meter=` a gvp_hip.metrics.RegressionMeter on the model's device, every `run` appends its B predictions and
+    targets to the meter inside the captured step (the warm-up passes of a capture add nothing, the padding pair is never
+    recorded): `meter.compute()` at the end of an epoch replaces the reference's `.item()` per step (train_model.py:609-636).
+
     One launch stages the batch into the bucket's padded static buffers, one replay runs the step.  Padding: padded
     residues / atoms are isolated nodes that belong to an extra (B+1)-th pair whose prediction the loss never reads, so
     every real pair's numbers and every gradient equal those of the eager step on the unpadded batch (padded rows have
     zero upstream gradient; tests/test_hip_models.py::test_graphed_train_step_equals_eager).  The gradients are the graph's
     static tensors: consume them (optimizer step) before the next `run` of the same bucket."""
 
-    def __init__(self, model, loss_fn, scaler=None, autocast=None, quantum=bucket_size, optimizer=None):
+    def __init__(self, model, loss_fn, scaler=None, autocast=None, quantum=bucket_size, optimizer=None, meter=None):
         if _lib.bridge() is None:
             # the capture-safety check below (_check_no_foreign_graph) lives in the C++ bridge: without it a forgotten eager
             # `loss` / `pred` turns the next capture into a segmentation fault inside hipStreamEndCapture
@@ -247,6 +251,13 @@ class GraphedTrainStep(_BucketedGraphs):
                 raise ValueError("GraphedTrainStep(optimizer=...): the optimizer must hold every trainable parameter of the model "
                                  "(FusedAdam(model.parameters(), ...))")
             self._opt_slots, self._opt_key = [slot[id(p)] for p in self.params], optimizer.hyper_key()
+        self.meter = meter
+        if meter is not None:
+            from .metrics import RegressionMeter
+            if not isinstance(meter, RegressionMeter):
+                raise TypeError(f"GraphedTrainStep(meter=...) captures a gvp_hip.metrics.RegressionMeter, not a {type(meter).__name__}")
+            if meter.device != self.device:
+                raise ValueError(f"GraphedTrainStep(meter=...): the meter lives on {meter.device}, the model on {self.device}")
 
     def _check_not_pair_parallel(self):
         if getattr(self.model, "_pair_parallel", False):
@@ -301,6 +312,9 @@ class GraphedTrainStep(_BucketedGraphs):
             for i, g in zip(self._opt_slots, grads):
                 full[i] = g
             self.optimizer.apply(full, scaler=self.scaler, dry=not torch.cuda.is_current_stream_capturing())
+        if self.meter is not None:
+            # the B real predictions and targets of this step (never the padding pair); dry in the warm-up passes, as above
+            self.meter.update(pred[:B].detach(), b.target, dry=not torch.cuda.is_current_stream_capturing())
         return loss.detach(), pred[:B].detach(), grads
 
     @staticmethod
