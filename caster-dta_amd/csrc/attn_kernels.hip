@@ -23,7 +23,7 @@
 
 #include <type_traits>
 
-#include "../../include/caster_gvp.h"
+#include "gvp_host.h"
 
 namespace {
 
@@ -384,11 +384,6 @@ __global__ __launch_bounds__(TPB) void attn_weights_kernel(Args a) {
   }
 }
 
-int status() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
-}
-
 // `long_first`: which of two problems gets the low workgroup indices -- the one whose waves loop longest (1: over the
 // keys, the forward and d Q kernels; 2: over the queries, the d K / d V kernel).  Workgroups start in index order: with
 // the residues -> atoms direction first, its 10k three-tile waves filled the chip and the 1.8k nineteen-tile waves of the
@@ -430,8 +425,8 @@ int cgvp_attn_fwd(const cgvp_attn_problem* probs, int32_t num_problems, int64_t 
   a.scale = scale;
   if (num_pairs == 0) return 0;
   const int64_t units = ((int64_t)a.p[0].units_q + a.p[1].units_q) * heads;
-  hipLaunchKernelGGL(attn_fwd_kernel, dim3((unsigned)((units + WPB - 1) / WPB)), dim3(TPB), 0, (hipStream_t)stream, a);
-  return status();
+  launch<attn_fwd_kernel>(dim3((unsigned)((units + WPB - 1) / WPB)), dim3(TPB), 0, (hipStream_t)stream, a);
+  return launch_status();
 }
 
 int cgvp_attn_weights(const cgvp_attn_problem* probs, int32_t num_problems, int64_t num_pairs, int32_t heads, float scale,
@@ -443,8 +438,8 @@ int cgvp_attn_weights(const cgvp_attn_problem* probs, int32_t num_problems, int6
     if (!probs[i].weights || probs[i].weights_lq < 0 || probs[i].weights_lk < 0) return CGVP_ERR_BAD_ARG;
   if (num_pairs == 0) return 0;
   const int64_t tiles = (int64_t)a.p[0].units_q + a.p[1].units_q;
-  hipLaunchKernelGGL(attn_weights_kernel, dim3((unsigned)((tiles + WPB - 1) / WPB)), dim3(TPB), 0, (hipStream_t)stream, a);
-  return status();
+  launch<attn_weights_kernel>(dim3((unsigned)((tiles + WPB - 1) / WPB)), dim3(TPB), 0, (hipStream_t)stream, a);
+  return launch_status();
 }
 
 int cgvp_attn_bwd(const cgvp_attn_problem* probs, int32_t num_problems, int64_t num_pairs, int32_t heads, float scale,
@@ -460,9 +455,9 @@ int cgvp_attn_bwd(const cgvp_attn_problem* probs, int32_t num_problems, int64_t 
   if (num_pairs == 0) return 0;
   const int64_t uq = ((int64_t)a.p[0].units_q + a.p[1].units_q) * heads;
   const int64_t uk = ((int64_t)a.p[0].units_k + a.p[1].units_k) * heads;
-  hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3((unsigned)((uq + WPB - 1) / WPB)), dim3(TPB), 0, (hipStream_t)stream, a);
-  hipLaunchKernelGGL(attn_bwd_dkv_kernel, dim3((unsigned)((uk + WPB - 1) / WPB)), dim3(TPB), 0, (hipStream_t)stream, ak);
-  return status();
+  launch<attn_bwd_dq_kernel>(dim3((unsigned)((uq + WPB - 1) / WPB)), dim3(TPB), 0, (hipStream_t)stream, a);
+  launch<attn_bwd_dkv_kernel>(dim3((unsigned)((uk + WPB - 1) / WPB)), dim3(TPB), 0, (hipStream_t)stream, ak);
+  return launch_status();
 }
 
 }  // extern "C"

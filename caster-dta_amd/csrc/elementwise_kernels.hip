@@ -83,15 +83,14 @@ gvp::RngArgs args_of(const cgvp_rng* rng) {
 // The backward reads act' off the sign of the saved OUTPUT (y > 0 ? 1 : slope), which is the sign of t only for slope >= 0.
 bool slope_ok(float slope) { return slope >= 0.f && slope <= 3.402823466e38f; }
 template <int MODE>
-int launch(const float* a, const float* b, const cgvp_rng* rng, float slope, int64_t rows, int32_t dim, float* out, void* stream) {
+int drop(const float* a, const float* b, const cgvp_rng* rng, float slope, int64_t rows, int32_t dim, float* out, void* stream) {
   if (rows == 0) return 0;
   const int64_t total = rows * (dim / 8);
   int64_t g = (total + TPB - 1) / TPB;
   if (g > 4096) g = 4096;
-  hipLaunchKernelGGL(drop_kernel<MODE>, dim3((unsigned)g), dim3(TPB), 0, (hipStream_t)stream, a, b, args_of(rng), slope, rows,
-                     dim / 8, out);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  launch<drop_kernel<MODE>>(dim3((unsigned)g), dim3(TPB), 0, (hipStream_t)stream, a, b, args_of(rng), slope, rows,
+                            dim / 8, out);
+  return launch_status();
 }
 
 }  // namespace
@@ -101,18 +100,18 @@ extern "C" {
 int cgvp_dropout_add(const float* a, const float* x, const cgvp_rng* rng, int64_t rows, int32_t dim, float* y, void* stream) {
   if (int rc = check(a, rng, rows, dim, y)) return rc;
   if ((uintptr_t)x & 15) return CGVP_ERR_BAD_ARG;
-  return launch<0>(a, x, rng, 0.f, rows, dim, y, stream);
+  return drop<0>(a, x, rng, 0.f, rows, dim, y, stream);
 }
 
 int cgvp_dropout_scale(const float* g, const cgvp_rng* rng, int64_t rows, int32_t dim, float* out, void* stream) {
   if (int rc = check(g, rng, rows, dim, out)) return rc;
-  return launch<1>(g, nullptr, rng, 0.f, rows, dim, out, stream);
+  return drop<1>(g, nullptr, rng, 0.f, rows, dim, out, stream);
 }
 
 int cgvp_act_dropout_fwd(const float* t, const cgvp_rng* rng, float slope, int64_t rows, int32_t dim, float* y, void* stream) {
   if (int rc = check(t, rng, rows, dim, y)) return rc;
   if (!slope_ok(slope)) return CGVP_ERR_BAD_ARG;
-  return launch<2>(t, nullptr, rng, slope, rows, dim, y, stream);
+  return drop<2>(t, nullptr, rng, slope, rows, dim, y, stream);
 }
 
 int cgvp_act_dropout_bwd(const float* g, const float* y, const cgvp_rng* rng, float slope, int64_t rows, int32_t dim, float* gt,
@@ -120,7 +119,7 @@ int cgvp_act_dropout_bwd(const float* g, const float* y, const cgvp_rng* rng, fl
   if (int rc = check(g, rng, rows, dim, gt)) return rc;
   if (rows > 0 && (!y || ((uintptr_t)y & 15))) return CGVP_ERR_BAD_ARG;
   if (!slope_ok(slope)) return CGVP_ERR_BAD_ARG;
-  return launch<3>(g, y, rng, slope, rows, dim, gt, stream);
+  return drop<3>(g, y, rng, slope, rows, dim, gt, stream);
 }
 
 }  // extern "C"

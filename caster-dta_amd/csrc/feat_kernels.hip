@@ -16,7 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/caster_gvp.h"
+#include "gvp_host.h"
 
 namespace {
 
@@ -73,7 +73,6 @@ extern "C" int cgvp_edge_featurise(const float* ca_xyz, const int64_t* seq_index
   if (num_nodes == 0 || !ca_xyz || !seq_index || !edge_index || !e_s || !e_v || ((uintptr_t)e_s & 15)) return CGVP_ERR_BAD_ARG;
   FeatArgs a{ca_xyz, seq_index, edge_index, num_nodes, num_edges, e_s, e_v};
   const int64_t threads = num_edges * 8;
-  hipLaunchKernelGGL(edge_feat_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-  const hipError_t err = hipGetLastError();
-  return err == hipSuccess ? 0 : (int)err;
+  launch<edge_feat_kernel>(dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  return launch_status();
 }

@@ -3,7 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/caster_gvp.h"
+#include "gvp_host.h"
 #include "gvp_math.h"
 #include "gvp_rng.h"
 
@@ -22,37 +22,7 @@ struct QuadOffsets {
 #endif
 constexpr int kBwdMaxGrid = CGVP_BWD_MAX_GRID;    // persistent workgroups of the backward kernels (one per CU) = slab rows per stage
 
-#include <atomic>
 #include <type_traits>
-
-// One launch of `Kernel`; returns 0, a CGVP_ERR_* code or the hipError_t of a failed attribute call.  A launch that needs
-// more dynamic LDS than the 64 KB every kernel may use raises hipFuncAttributeMaxDynamicSharedMemorySize to `reserve`
-// bytes first, ONCE per kernel and device (hipFuncSetAttribute is a host call of tens of microseconds; a backward pass
-// made 13 of them): the static below exists per instantiation = per kernel and holds the bytes set on each device.  A
-// later launch of the same kernel that asks for more than was set is refused instead of faulting on the device.
-template <auto Kernel, class... A>
-int launch_reserving(dim3 grid, dim3 block, size_t lds, size_t reserve, hipStream_t st, const A&... args) {
-  if (lds > 64 * 1024) {
-    static std::atomic<int> set_bytes[64];      // zero = not set on that device yet; idempotent, benign process state
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::atomic<int>& set = set_bytes[dev & 63];
-    int have = set.load(std::memory_order_acquire);
-    if (!have && lds <= reserve) {
-      if (hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)reserve))
-        return (int)err;
-      set.store(have = (int)reserve, std::memory_order_release);
-    }
-    if (lds > (size_t)have) return CGVP_ERR_BAD_ARG;
-  }
-  hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
-  return 0;
-}
-// the usual case: the kernel has ONE dynamic LDS size
-template <auto Kernel, class... A>
-int launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... args) {
-  return launch_reserving<Kernel>(grid, block, lds, lds, st, args...);
-}
 
 // Runtime value -> compile-time tag of a generic lambda, so that every combination of kernel template flags is written once.
 // with_policy: `f(Tag<ST>{})` for the storage tag type ST of a tile policy index; KINDS says whether the two layer-kind

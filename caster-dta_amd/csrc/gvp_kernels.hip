@@ -54,11 +54,6 @@ inline EncLayout cvt(const cgvp_layout& l) {
 }
 inline int num_convs_of(const cgvp_layout& l) { return l.conv_stride > 0 ? (l.ln_out - l.conv0) / l.conv_stride : 0; }
 
-inline int launch_status() {
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
-}
-
 // what every fine-grained backward entry point looks up first: the image offsets and the slab row sizes of the layout
 struct BwdLookup : QuadOffsets { quad::BwdBlocks blk; };
 inline int bwd_lookup(const cgvp_layout& l, BwdLookup* o) {
@@ -95,7 +90,7 @@ inline void zero_words(void* p, size_t words, hipStream_t s) {
   if (words == 0 || !p) return;
   size_t blocks = (words + 1023) / 1024;                     // 4 words per thread at most
   if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)blocks), dim3(256), 0, s, reinterpret_cast<uint32_t*>(p), words);
+  launch<zero_words_kernel>(dim3((unsigned)blocks), dim3(256), 0, s, reinterpret_cast<uint32_t*>(p), words);
 }
 
 __global__ void csr_count_kernel(const int64_t* __restrict__ ei, int64_t N, int64_t E,
@@ -752,20 +747,20 @@ int csr_build(const int64_t* edge_index, int64_t N, int64_t E, int32_t* rowptr, 
   int32_t* tmp = ids_scratch;
   const int B = 256;
   if (E > 0 && work_is_zero != 2)     // 2: cgvp_lba_pass_begin already counted into `work`
-    hipLaunchKernelGGL(csr_count_kernel, dim3((unsigned)((E + B - 1) / B)), dim3(B), 0, s, edge_index, N, E, work, rng_state, rng_out);
+    launch<csr_count_kernel>(dim3((unsigned)((E + B - 1) / B)), dim3(B), 0, s, edge_index, N, E, work, rng_state, rng_out);
   else if (rng_state)
-    hipLaunchKernelGGL(rng_next_kernel, dim3(1), dim3(1), 0, s, rng_state, rng_out);
+    launch<rng_next_kernel>(dim3(1), dim3(1), 0, s, rng_state, rng_out);
   if (N < SCAN_MULTI_MAX) {
-    hipLaunchKernelGGL(csr_scan_multi_kernel, dim3((unsigned)((N + 1 + SCAN_MULTI_CHUNK - 1) / SCAN_MULTI_CHUNK)),
-                       dim3(SCAN_MULTI_T), 0, s, work, (int32_t)N, (int32_t)counters, rowptr);
+    launch<csr_scan_multi_kernel>(dim3((unsigned)((N + 1 + SCAN_MULTI_CHUNK - 1) / SCAN_MULTI_CHUNK)),
+                                  dim3(SCAN_MULTI_T), 0, s, work, (int32_t)N, (int32_t)counters, rowptr);
   } else {
     const int64_t tile = N < SCAN_LDS ? (N + 3) / 4 * 4 : SCAN_LDS;
-    hipLaunchKernelGGL(csr_scan_kernel, dim3(1), dim3(1024), (size_t)(tile + 1024 + 32) * sizeof(int32_t), s, work, N, rowptr);
+    if (int rc = launch<csr_scan_kernel>(dim3(1), dim3(1024), (size_t)(tile + 1024 + 32) * sizeof(int32_t), s, work, N, rowptr)) return rc;
   }
-  if (E > 0) hipLaunchKernelGGL(csr_fill_kernel, dim3((unsigned)((E + B - 1) / B)), dim3(B), 0, s, edge_index, N, E, rowptr, work, tmp, edst);
+  if (E > 0) launch<csr_fill_kernel>(dim3((unsigned)((E + B - 1) / B)), dim3(B), 0, s, edge_index, N, E, rowptr, work, tmp, edst);
   const int64_t span = E > counters ? E : counters;
-  hipLaunchKernelGGL(csr_rank_kernel, dim3((unsigned)((span + B - 1) / B)), dim3(B), 0, s, edge_index, N, E, counters, rowptr, tmp,
-                     edst, eperm, esrc, work);
+  launch<csr_rank_kernel>(dim3((unsigned)((span + B - 1) / B)), dim3(B), 0, s, edge_index, N, E, counters, rowptr, tmp,
+                          edst, eperm, esrc, work);
   return launch_status();
 }
 
@@ -787,17 +782,17 @@ int src_index(const int32_t* rowptr, const int32_t* esrc, int64_t N, int64_t E, 
   zero_words(cnt, (size_t)counters, s);
   const int B = 256;
   const unsigned eb = (unsigned)((E + B - 1) / B);
-  if (E > 0) hipLaunchKernelGGL(src_count_kernel, dim3(eb), dim3(B), 0, s, esrc, rowptr, N, cnt);
+  if (E > 0) launch<src_count_kernel>(dim3(eb), dim3(B), 0, s, esrc, rowptr, N, cnt);
   if (N < SCAN_MULTI_MAX) {
-    hipLaunchKernelGGL(csr_scan_multi_kernel, dim3((unsigned)((N + 1 + SCAN_MULTI_CHUNK - 1) / SCAN_MULTI_CHUNK)),
-                       dim3(SCAN_MULTI_T), 0, s, cnt, (int32_t)N, (int32_t)counters, sptr);
+    launch<csr_scan_multi_kernel>(dim3((unsigned)((N + 1 + SCAN_MULTI_CHUNK - 1) / SCAN_MULTI_CHUNK)),
+                                  dim3(SCAN_MULTI_T), 0, s, cnt, (int32_t)N, (int32_t)counters, sptr);
   } else {
     const int64_t tile = N < SCAN_LDS ? (N + 3) / 4 * 4 : SCAN_LDS;
-    hipLaunchKernelGGL(csr_scan_kernel, dim3(1), dim3(1024), (size_t)(tile + 1024 + 32) * sizeof(int32_t), s, cnt, N, sptr);
+    if (int rc = launch<csr_scan_kernel>(dim3(1), dim3(1024), (size_t)(tile + 1024 + 32) * sizeof(int32_t), s, cnt, N, sptr)) return rc;
   }
   if (E > 0) {
-    hipLaunchKernelGGL(src_fill_kernel, dim3(eb), dim3(B), 0, s, esrc, rowptr, N, sptr, cnt, tmp);
-    hipLaunchKernelGGL(src_rank_kernel, dim3(eb), dim3(B), 0, s, esrc, rowptr, N, sptr, tmp, spos);
+    launch<src_fill_kernel>(dim3(eb), dim3(B), 0, s, esrc, rowptr, N, sptr, cnt, tmp);
+    launch<src_rank_kernel>(dim3(eb), dim3(B), 0, s, esrc, rowptr, N, sptr, tmp, spos);
   }
   return launch_status();
 }
@@ -816,7 +811,7 @@ int cgvp_csr_collate(const int32_t* st_rowptr, const int32_t* st_eperm, const in
   if (!st_rowptr || !st_node_off || !st_edge_off || !sel || !b_node_off || !b_edge_off) return CGVP_ERR_BAD_ARG;
   CsrCollateArgs a{st_rowptr, st_eperm, st_esrc, st_edst, st_node_off, st_edge_off, sel, b_node_off, b_edge_off, B,
                    rowptr, eperm, esrc, edst, table_mode ? 1 : 0};
-  hipLaunchKernelGGL(csr_collate_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, a);
+  launch<csr_collate_kernel>(dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, a);
   return launch_status();
 }
 
@@ -891,9 +886,9 @@ int cgvp_node_embed_fwd(const cgvp_dims* dims, const cgvp_layout* layout, const 
   const dim3 grid((unsigned)((N + WAVE - 1) / WAVE));
   hipStream_t st = (hipStream_t)stream;
   switch (layout->nt_node) {   // one-hot width is a compile-time constant of the kernel
-    case 0: hipLaunchKernelGGL(node_embed_kernel<0>, grid, dim3(WAVE), 0, st, a); break;
-    case 20: hipLaunchKernelGGL(node_embed_kernel<20>, grid, dim3(WAVE), 0, st, a); break;
-    case 21: hipLaunchKernelGGL(node_embed_kernel<21>, grid, dim3(WAVE), 0, st, a); break;
+    case 0: launch<node_embed_kernel<0>>(grid, dim3(WAVE), 0, st, a); break;
+    case 20: launch<node_embed_kernel<20>>(grid, dim3(WAVE), 0, st, a); break;
+    case 21: launch<node_embed_kernel<21>>(grid, dim3(WAVE), 0, st, a); break;
     default: return CGVP_ERR_UNSUPPORTED_DIMS;
   }
   return launch_status();
@@ -934,8 +929,8 @@ int cgvp_conv_fwd(const cgvp_dims* dims, const cgvp_layout* layout, const float*
   const dim3 grid((unsigned)((N + npw - 1) / npw));
   hipStream_t st = (hipStream_t)stream;
   switch (layout->nt_edge) {
-    case 0: hipLaunchKernelGGL(conv_fwd_kernel<0>, grid, dim3(WAVE), 0, st, a); break;
-    case 1: hipLaunchKernelGGL(conv_fwd_kernel<1>, grid, dim3(WAVE), 0, st, a); break;
+    case 0: launch<conv_fwd_kernel<0>>(grid, dim3(WAVE), 0, st, a); break;
+    case 1: launch<conv_fwd_kernel<1>>(grid, dim3(WAVE), 0, st, a); break;
     default: return CGVP_ERR_UNSUPPORTED_DIMS;
   }
   return launch_status();
@@ -987,8 +982,8 @@ int cgvp_node_update_fwd(const cgvp_dims* dims, const cgvp_layout* layout, const
   if (policy_of(dims)) return CGVP_ERR_UNSUPPORTED_DIMS;
   NodeUpdateArgs a{params, cvt(*layout), layer, h, dh, N, h_out, out};
   dim3 grid((unsigned)((N + WAVE - 1) / WAVE));
-  if (with_head) hipLaunchKernelGGL(node_update_kernel<true>, grid, dim3(WAVE), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(node_update_kernel<false>, grid, dim3(WAVE), 0, (hipStream_t)stream, a);
+  if (with_head) launch<node_update_kernel<true>>(grid, dim3(WAVE), 0, (hipStream_t)stream, a);
+  else launch<node_update_kernel<false>>(grid, dim3(WAVE), 0, (hipStream_t)stream, a);
   return launch_status();
 }
 
@@ -1221,15 +1216,15 @@ int cgvp_gine_conv_fwd(const float* x, const int64_t* ntypes, int32_t num_ntypes
   GineArgs a{x, ntypes, num_ntypes, eattr, etypes, num_etypes, edge_dim, rowptr, eperm, esrc, N, cin,
              chid, cout, w->eps, w->we, w->be, w->w0, w->b0, w->w1, w->b1, act_slope, out, mask, ra};
   const size_t lds = (size_t)(chid * (cin + 1) + cout * (chid + 1) + 2 * GINE_APB * WAVE) * sizeof(float);
-  hipLaunchKernelGGL(gine_conv_kernel, dim3((unsigned)((N + GINE_APB - 1) / GINE_APB)),
-                     dim3(WAVE * GINE_APB), lds, (hipStream_t)stream, a);
+  launch<gine_conv_kernel>(dim3((unsigned)((N + GINE_APB - 1) / GINE_APB)),
+                           dim3(WAVE * GINE_APB), lds, (hipStream_t)stream, a);
   return launch_status();
 }
 
 int cgvp_rng_next(uint64_t* state, uint64_t* out, void* stream) {
   if (!state || !out || ((uintptr_t)state & 7) || ((uintptr_t)out & 7)) return CGVP_ERR_BAD_ARG;
-  hipLaunchKernelGGL(rng_next_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream,
-                     reinterpret_cast<unsigned long long*>(state), reinterpret_cast<unsigned long long*>(out));
+  launch<rng_next_kernel>(dim3(1), dim3(1), 0, (hipStream_t)stream,
+                          reinterpret_cast<unsigned long long*>(state), reinterpret_cast<unsigned long long*>(out));
   return launch_status();
 }
 
@@ -1239,8 +1234,8 @@ int cgvp_dropout_masks(const cgvp_rng* rng, int32_t num_masks, int64_t N, int32_
   if (N == 0) return 0;
   MaskArgs a{rng_args(rng, 0), num_masks, N, width, out};
   const int64_t total = (int64_t)num_masks * N * (width / 4);
-  hipLaunchKernelGGL(dropout_masks_kernel, dim3((unsigned)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256)), dim3(256), 0,
-                     (hipStream_t)stream, a);
+  launch<dropout_masks_kernel>(dim3((unsigned)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256)), dim3(256), 0,
+                               (hipStream_t)stream, a);
   return launch_status();
 }
 

@@ -1436,11 +1436,11 @@ template <bool ADD>
 void launch_reduce_segments(const SegTable& t, int nsegs, int maxlen, int maxrows, float* grad_params, hipStream_t st,
                             int overwrite) {
   if (maxrows <= 32) {
-    hipLaunchKernelGGL(reduce_segments_rows_kernel<ADD>, dim3((maxlen + 255) / 256, nsegs), dim3(256), 0, st, t, grad_params, overwrite);
+    launch<reduce_segments_rows_kernel<ADD>>(dim3((maxlen + 255) / 256, nsegs), dim3(256), 0, st, t, grad_params, overwrite);
     return;
   }
-  hipLaunchKernelGGL(reduce_segments_kernel<ADD>, dim3((maxlen + RED_COLS - 1) / RED_COLS, nsegs), dim3(RED_COLS * RED_RG), 0,
-                     st, t, grad_params, overwrite);
+  launch<reduce_segments_kernel<ADD>>(dim3((maxlen + RED_COLS - 1) / RED_COLS, nsegs), dim3(RED_COLS * RED_RG), 0,
+                                      st, t, grad_params, overwrite);
 }
 
 int reduce_segments(const cgvp_segment* segs, int nsegs, float* grad_params, hipStream_t st, int overwrite, bool store_only) {
@@ -1464,10 +1464,10 @@ int src_sum(int width, const float* rows, const float* self, const int32_t* sptr
   SrcSumArgs a{rows, self, sptr, spos, rowptr, slot, waves, N, out};
   const unsigned blocks = (unsigned)((N * width + 255) / 256);
   switch (width) {
-    case 16: hipLaunchKernelGGL(src_sum_kernel<16>, dim3(blocks), dim3(256), 0, st, a); return 0;
-    case ROW: hipLaunchKernelGGL(src_sum_kernel<ROW>, dim3(blocks), dim3(256), 0, st, a); return 0;
-    case 41: hipLaunchKernelGGL(src_sum_kernel<41>, dim3(blocks), dim3(256), 0, st, a); return 0;
-    case 52: hipLaunchKernelGGL(src_sum_kernel<52>, dim3(blocks), dim3(256), 0, st, a); return 0;
+    case 16: return launch<src_sum_kernel<16>>(dim3(blocks), dim3(256), 0, st, a);
+    case ROW: return launch<src_sum_kernel<ROW>>(dim3(blocks), dim3(256), 0, st, a);
+    case 41: return launch<src_sum_kernel<41>>(dim3(blocks), dim3(256), 0, st, a);
+    case 52: return launch<src_sum_kernel<52>>(dim3(blocks), dim3(256), 0, st, a);
     default: return CGVP_ERR_UNSUPPORTED_DIMS;
   }
 }
@@ -1476,10 +1476,10 @@ int conv_bwd_max_waves() { return BW_MAX_GRID * 8; }
 
 int reduce_slab(const float* slab, int rows, int stride, int col0, int len, float* dst, hipStream_t st) {
   if (rows <= 32) {            // a handful of rows: one thread per column, small workgroups that fit beside anything
-    hipLaunchKernelGGL(reduce_rows_kernel, dim3((len + 255) / 256), dim3(256), 0, st, slab, rows, stride, col0, len, dst);
+    launch<reduce_rows_kernel>(dim3((len + 255) / 256), dim3(256), 0, st, slab, rows, stride, col0, len, dst);
     return 0;
   }
-  hipLaunchKernelGGL(reduce_slab_kernel, dim3((len + RED_COLS - 1) / RED_COLS), dim3(RED_COLS * RED_RG), 0, st, slab, rows, stride, col0, len, dst);
+  launch<reduce_slab_kernel>(dim3((len + RED_COLS - 1) / RED_COLS), dim3(RED_COLS * RED_RG), 0, st, slab, rows, stride, col0, len, dst);
   return 0;
 }
 

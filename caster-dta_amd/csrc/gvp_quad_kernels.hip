@@ -680,8 +680,8 @@ __global__ __launch_bounds__(WAVE * CW) __attribute__((amdgpu_waves_per_eu(2, 2)
 template <int NTN, int NTE>
 int prepare_impl(const EncLayout& L, int num_convs, int packed, const float* params, float* image, hipStream_t st) {
   const int total = Image<NTN, NTE>::total(num_convs);
-  hipLaunchKernelGGL((lba_prepare_kernel<NTN, NTE>), dim3((total + 255) / 256), dim3(256), 0, st, params, L,
-                     num_convs, packed, image);
+  launch<lba_prepare_kernel<NTN, NTE>>(dim3((total + 255) / 256), dim3(256), 0, st, params, L,
+                                       num_convs, packed, image);
   return 0;
 }
 

@@ -172,8 +172,7 @@ int cgvp_linear_wgrad(const float* x, const float* gy, int64_t R, int32_t I, int
              : ntw <= 5 ? launch_wgrad<5, 144>(grid, lds, st, a) : launch_wgrad<9, 256>(grid, lds, st, a)) return rc;
   cgvp_segment sg[2] = {{workspace, (int)grid.x, len, 0, O * I, 0}, {workspace, (int)grid.x, len, O * I, O, O * I}};
   quad::reduce_segments(sg, 2, out, st, 1);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_status();
 }
 
 }  // extern "C"

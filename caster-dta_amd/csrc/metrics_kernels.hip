@@ -23,6 +23,8 @@
 #include <stdint.h>
 
 #include "../../include/caster_gvp_metrics.h"
+#include "gvp_block_sum.h"
+#include "gvp_host.h"
 
 namespace {
 
@@ -47,27 +49,6 @@ __device__ inline int64_t rows_of(const int64_t* count_dev, int64_t max_rows) {
   if (!count_dev) return max_rows;
   const int64_t n = count_dev[0];
   return n < 0 ? 0 : (n > max_rows ? max_rows : n);
-}
-
-// K sums over the workgroup in a fixed order: lanes of a wave by halving, then the waves 0, 1, 2, 3; valid in thread 0
-template <int K, typename T>
-__device__ inline void block_sum(T (&acc)[K]) {
-  __shared__ T wave_sum[K][WAVES];
-  __syncthreads();                                           // (an earlier call's reader is done)
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    for (int off = 32; off > 0; off >>= 1) acc[k] += __shfl_down(acc[k], off, 64);
-    if ((threadIdx.x & 63) == 0) wave_sum[k][threadIdx.x >> 6] = acc[k];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      T total = wave_sum[k][0];
-      for (int w = 1; w < WAVES; ++w) total += wave_sum[k][w];
-      acc[k] = total;
-    }
-  }
 }
 
 __global__ void reset_kernel(int64_t* __restrict__ state) {
@@ -112,7 +93,7 @@ __global__ __launch_bounds__(THREADS) void moments1_kernel(const float* __restri
       acc[3] += fabs(d);
     }
   }
-  block_sum(acc);
+  block_sum<WAVES>(acc);
   if (threadIdx.x == 0)
     for (int k = 0; k < 4; ++k) partial[4 * (int64_t)blockIdx.x + k] = acc[k];
 }
@@ -124,7 +105,7 @@ __global__ __launch_bounds__(THREADS) void means_kernel(const double* __restrict
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
   for (int64_t c = threadIdx.x; c < chunks; c += THREADS)
     for (int k = 0; k < 4; ++k) acc[k] += partial[4 * c + k];
-  block_sum(acc);
+  block_sum<WAVES>(acc);
   if (threadIdx.x != 0) return;
   const double rows = (double)n;                             // n == 0: 0 / 0 = NaN, as the header says
   means->mean_p = acc[0] / rows;
@@ -150,7 +131,7 @@ __global__ __launch_bounds__(THREADS) void moments2_kernel(const float* __restri
       acc[2] += p * t;
     }
   }
-  block_sum(acc);
+  block_sum<WAVES>(acc);
   if (threadIdx.x == 0)
     for (int k = 0; k < 3; ++k) partial[3 * (int64_t)blockIdx.x + k] = acc[k];
 }
@@ -203,7 +184,7 @@ __global__ __launch_bounds__(THREADS) void pair_kernel(const float* __restrict__
     }
   }
   u64 acc[3] = {concordant, tied, comparable};
-  block_sum(acc);
+  block_sum<WAVES>(acc);
   if (threadIdx.x == 0)
     for (int k = 0; k < 3; ++k) partial[3 * (int64_t)blockIdx.x + k] = (int64_t)acc[k];
 }
@@ -217,11 +198,11 @@ __global__ __launch_bounds__(THREADS) void finish_kernel(const double* __restric
   double acc[3] = {0.0, 0.0, 0.0};
   for (int64_t c = threadIdx.x; c < chunks; c += THREADS)
     for (int k = 0; k < 3; ++k) acc[k] += moments[3 * c + k];
-  block_sum(acc);
+  block_sum<WAVES>(acc);
   u64 cnt[3] = {0, 0, 0};
   for (int64_t g = threadIdx.x; g < used; g += THREADS)
     for (int k = 0; k < 3; ++k) cnt[k] += (u64)pairs[3 * g + k];
-  block_sum(cnt);
+  block_sum<WAVES>(cnt);
   if (threadIdx.x != 0) return;
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
   const int64_t concordant = (int64_t)cnt[0], tied = (int64_t)cnt[1], comparable = (int64_t)cnt[2];
@@ -242,14 +223,6 @@ __global__ __launch_bounds__(THREADS) void finish_kernel(const double* __restric
   out_vals[5] = means->mean_t;
 }
 
-inline bool bad4(const void* p) { return !p || ((uintptr_t)p & 3); }
-inline bool bad8(const void* p) { return !p || ((uintptr_t)p & 7); }
-
-inline int launched() {
-  const hipError_t err = hipGetLastError();
-  return err == hipSuccess ? 0 : (int)err;
-}
-
 inline int64_t chunks_of(int64_t rows) { return (rows + CHUNK - 1) / CHUNK; }
 
 inline int64_t pair_grid_of(int64_t rows) {
@@ -265,21 +238,21 @@ inline int64_t workspace_of(int64_t rows) { return kPartials + 8 * (7 * chunks_o
 extern "C" int cgvp_metrics_version(void) { return CGVP_METRICS_VERSION; }
 
 extern "C" int cgvp_metrics_reset(int64_t* state, void* stream) {
-  if (bad8(state)) return CGVP_ERR_BAD_ARG;
-  hipLaunchKernelGGL(reset_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state);
-  return launched();
+  if (bad_ptr(state, 8)) return CGVP_ERR_BAD_ARG;
+  launch<reset_kernel>(dim3(1), dim3(1), 0, (hipStream_t)stream, state);
+  return launch_status();
 }
 
 extern "C" int cgvp_metrics_append(const float* pred, const float* target, int64_t n, float* pred_buf, float* target_buf,
                                    int64_t capacity, int64_t* state, int32_t dry, void* stream) {
-  if (n < 0 || capacity < 0 || capacity > MAX_ROWS || bad8(state)) return CGVP_ERR_BAD_ARG;
-  if (n > 0 && (bad4(pred) || bad4(target))) return CGVP_ERR_BAD_ARG;
-  if (capacity > 0 ? (bad4(pred_buf) || bad4(target_buf)) : (((uintptr_t)pred_buf | (uintptr_t)target_buf) & 3) != 0)
+  if (n < 0 || capacity < 0 || capacity > MAX_ROWS || bad_ptr(state, 8)) return CGVP_ERR_BAD_ARG;
+  if (n > 0 && (bad_ptr(pred, 4) || bad_ptr(target, 4))) return CGVP_ERR_BAD_ARG;
+  if (capacity > 0 ? (bad_ptr(pred_buf, 4) || bad_ptr(target_buf, 4)) : (((uintptr_t)pred_buf | (uintptr_t)target_buf) & 3) != 0)
     return CGVP_ERR_BAD_ARG;
   if (n == 0) return 0;
-  hipLaunchKernelGGL(append_kernel, dim3(1), dim3(THREADS), 0, (hipStream_t)stream, pred, target, n, pred_buf, target_buf,
-                     capacity, state, dry ? 1 : 0);
-  return launched();
+  launch<append_kernel>(dim3(1), dim3(THREADS), 0, (hipStream_t)stream, pred, target, n, pred_buf, target_buf,
+                        capacity, state, dry ? 1 : 0);
+  return launch_status();
 }
 
 extern "C" int64_t cgvp_metrics_workspace_bytes(int64_t max_rows) {
@@ -291,10 +264,10 @@ extern "C" int cgvp_metrics_compute(const float* pred_buf, const float* target_b
                                     int64_t max_rows, int64_t* out_counts, double* out_vals, void* workspace,
                                     int64_t workspace_bytes, void* stream) {
   if (max_rows < 0 || max_rows > MAX_ROWS) return CGVP_ERR_BAD_ARG;
-  if (max_rows > 0 ? (bad4(pred_buf) || bad4(target_buf)) : (((uintptr_t)pred_buf | (uintptr_t)target_buf) & 3) != 0)
+  if (max_rows > 0 ? (bad_ptr(pred_buf, 4) || bad_ptr(target_buf, 4)) : (((uintptr_t)pred_buf | (uintptr_t)target_buf) & 3) != 0)
     return CGVP_ERR_BAD_ARG;
-  if ((count_dev && bad8(count_dev)) || bad8(out_counts) || bad8(out_vals)) return CGVP_ERR_BAD_ARG;
-  if (bad8(workspace) || workspace_bytes < workspace_of(max_rows)) return CGVP_ERR_BAD_ARG;
+  if ((count_dev && bad_ptr(count_dev, 8)) || bad_ptr(out_counts, 8) || bad_ptr(out_vals, 8)) return CGVP_ERR_BAD_ARG;
+  if (bad_ptr(workspace, 8) || workspace_bytes < workspace_of(max_rows)) return CGVP_ERR_BAD_ARG;
 
   hipStream_t st = (hipStream_t)stream;
   const int64_t chunks = chunks_of(max_rows), pair_grid = pair_grid_of(max_rows);
@@ -303,19 +276,19 @@ extern "C" int cgvp_metrics_compute(const float* pred_buf, const float* target_b
   double* part2 = part1 + 4 * chunks;
   int64_t* pairs = reinterpret_cast<int64_t*>(part2 + 3 * chunks);
   if (max_rows > 0) {
-    hipLaunchKernelGGL(moments1_kernel, dim3((unsigned)chunks), dim3(THREADS), 0, st, pred_buf, target_buf, count_dev,
-                       max_rows, part1);
-    if (const int rc = launched()) return rc;
-    hipLaunchKernelGGL(means_kernel, dim3(1), dim3(THREADS), 0, st, part1, count_dev, max_rows, means);
-    if (const int rc = launched()) return rc;
-    hipLaunchKernelGGL(moments2_kernel, dim3((unsigned)chunks), dim3(THREADS), 0, st, pred_buf, target_buf, count_dev,
-                       max_rows, means, part2);
-    if (const int rc = launched()) return rc;
-    hipLaunchKernelGGL(pair_kernel, dim3((unsigned)pair_grid), dim3(THREADS), 0, st, pred_buf, target_buf, count_dev,
-                       max_rows, pairs);
-    if (const int rc = launched()) return rc;
+    launch<moments1_kernel>(dim3((unsigned)chunks), dim3(THREADS), 0, st, pred_buf, target_buf, count_dev,
+                            max_rows, part1);
+    if (const int rc = launch_status()) return rc;
+    launch<means_kernel>(dim3(1), dim3(THREADS), 0, st, part1, count_dev, max_rows, means);
+    if (const int rc = launch_status()) return rc;
+    launch<moments2_kernel>(dim3((unsigned)chunks), dim3(THREADS), 0, st, pred_buf, target_buf, count_dev,
+                            max_rows, means, part2);
+    if (const int rc = launch_status()) return rc;
+    launch<pair_kernel>(dim3((unsigned)pair_grid), dim3(THREADS), 0, st, pred_buf, target_buf, count_dev,
+                        max_rows, pairs);
+    if (const int rc = launch_status()) return rc;
   }
-  hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(THREADS), 0, st, part2, pairs, pair_grid, means, count_dev, max_rows,
-                     out_counts, out_vals);
-  return launched();
+  launch<finish_kernel>(dim3(1), dim3(THREADS), 0, st, part2, pairs, pair_grid, means, count_dev, max_rows,
+                        out_counts, out_vals);
+  return launch_status();
 }

@@ -97,6 +97,16 @@ int grid_for(int64_t rows) {
   return (int)(wgs < 1 ? 1 : (wgs > MAX_WGS ? MAX_WGS : wgs));
 }
 bool dim_ok(int dim) { return dim == 64 || dim == 128 || dim == 256 || dim == 512; }
+// `f(std::integral_constant<int, VPL>{})` for the values per lane of a row of `dim` (dim_ok) floats
+template <class F>
+int with_vpl(int dim, F&& f) {
+  switch (dim) {
+    case 64: return f(std::integral_constant<int, 1>{});
+    case 128: return f(std::integral_constant<int, 2>{});
+    case 256: return f(std::integral_constant<int, 4>{});
+    default: return f(std::integral_constant<int, 8>{});
+  }
+}
 
 }  // namespace
 
@@ -110,11 +120,10 @@ int cgvp_layer_norm_fwd(const float* x, const float* gamma, const float* beta, i
   if (!x || !y || !mean || !rstd) return CGVP_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)((rows + WPB - 1) / WPB < 4096 ? (rows + WPB - 1) / WPB : 4096));
-#define LAUNCH(V) hipLaunchKernelGGL(layer_norm_fwd_kernel<V>, grid, dim3(TPB), 0, st, x, gamma, beta, rows, eps, y, mean, rstd)
-  switch (dim) { case 64: LAUNCH(1); break; case 128: LAUNCH(2); break; case 256: LAUNCH(4); break; default: LAUNCH(8); }
-#undef LAUNCH
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  with_vpl(dim, [&](auto vpl) {
+    return launch<layer_norm_fwd_kernel<vpl.value>>(grid, dim3(TPB), 0, st, x, gamma, beta, rows, eps, y, mean, rstd);
+  });
+  return launch_status();
 }
 
 int64_t cgvp_layer_norm_bwd_workspace_floats(int64_t rows, int32_t dim) {
@@ -134,13 +143,12 @@ int cgvp_layer_norm_bwd(const float* gy, const float* x, const float* mean, cons
   }
   if (!gy || !x || !mean || !rstd || !gx || !workspace) return CGVP_ERR_BAD_ARG;
   const int G = grid_for(rows);
-#define LAUNCH(V) hipLaunchKernelGGL(layer_norm_bwd_kernel<V>, dim3(G), dim3(TPB), 0, st, gy, x, mean, rstd, gamma, rows, gx, workspace)
-  switch (dim) { case 64: LAUNCH(1); break; case 128: LAUNCH(2); break; case 256: LAUNCH(4); break; default: LAUNCH(8); }
-#undef LAUNCH
+  with_vpl(dim, [&](auto vpl) {
+    return launch<layer_norm_bwd_kernel<vpl.value>>(dim3(G), dim3(TPB), 0, st, gy, x, mean, rstd, gamma, rows, gx, workspace);
+  });
   cgvp_segment sg[1] = {{workspace, G, 2 * dim, 0, 2 * dim, 0}};
   quad::reduce_segments(sg, 1, g_gamma_beta, st, 1);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_status();
 }
 
 }  // extern "C"

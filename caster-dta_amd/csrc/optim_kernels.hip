@@ -23,10 +23,12 @@
 #include <stdint.h>
 
 #include "../../include/caster_gvp_optim.h"
+#include "gvp_block_sum.h"
+#include "gvp_host.h"
 
 namespace {
 
-constexpr int CHUNK = CGVP_OPTIM_CHUNK, THREADS = 256, CAP = CGVP_OPTIM_MAX_SEGMENTS;
+constexpr int CHUNK = CGVP_OPTIM_CHUNK, THREADS = 256, WAVES = THREADS / 64, CAP = CGVP_OPTIM_MAX_SEGMENTS;
 constexpr int GROUPS = CHUNK / (4 * THREADS);          // float4 groups per thread and chunk
 static_assert(CHUNK % (4 * THREADS) == 0, "a chunk is a whole number of float4 rounds of the workgroup");
 
@@ -98,38 +100,26 @@ __device__ inline void store4(float* p, bool vec, int valid, float4 r) {
   if (valid > 3) p[3] = r.w;
 }
 
-// sum over the workgroup in a fixed order: lanes of a wave by halving, then the four waves 0, 1, 2, 3; valid in thread 0
-__device__ inline double block_sum(double acc) {
-  __shared__ double wave_sum[THREADS / 64];
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-  if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  double total = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < THREADS / 64; ++w) total += wave_sum[w];
-  return total;
-}
-
 __global__ __launch_bounds__(THREADS) void norm_kernel(Table t, double* __restrict__ partial) {
   const int chunk = blockIdx.x, s = segment_of(t, chunk);
   const int64_t off = (int64_t)(chunk - t.first[s]) * CHUNK, left = t.seg[s].numel - off;
   const int n = left < CHUNK ? (int)left : CHUNK;
   const float* __restrict__ g = t.seg[s].grad + off;
   const bool vec = aligned16(g);
-  double acc = 0.0;
+  double acc[1] = {0.0};
 #pragma unroll
   for (int k = 0; k < GROUPS; ++k) {
     const int i = 4 * (k * THREADS + (int)threadIdx.x);
     if (i < n) {
       const float4 x = load4(g + i, vec, n - i < 4 ? n - i : 4);
-      acc += (double)x.x * (double)x.x;
-      acc += (double)x.y * (double)x.y;
-      acc += (double)x.z * (double)x.z;
-      acc += (double)x.w * (double)x.w;
+      acc[0] += (double)x.x * (double)x.x;
+      acc[0] += (double)x.y * (double)x.y;
+      acc[0] += (double)x.z * (double)x.z;
+      acc[0] += (double)x.w * (double)x.w;
     }
   }
-  const double total = block_sum(acc);
-  if (threadIdx.x == 0) partial[chunk] = total;
+  block_sum<WAVES>(acc);                                     // fixed order (gvp_block_sum.h); valid in thread 0
+  if (threadIdx.x == 0) partial[chunk] = acc[0];
 }
 
 // base^n for a whole n >= 0 by repeated squaring
@@ -141,10 +131,11 @@ __device__ inline double pow_whole(double base, uint32_t n) {
 }
 
 __global__ __launch_bounds__(THREADS) void finish_kernel(FinishArgs a) {
-  double acc = 0.0;
-  for (int64_t i = threadIdx.x; i < a.chunks; i += THREADS) acc += a.partial[i];
-  const double total = block_sum(acc);
+  double acc[1] = {0.0};
+  for (int64_t i = threadIdx.x; i < a.chunks; i += THREADS) acc[0] += a.partial[i];
+  block_sum<WAVES>(acc);
   if (threadIdx.x != 0) return;
+  const double total = acc[0];
   const bool bad = !isfinite(total);
   const double inv = a.scale ? 1.0 / (double)a.scale[0] : 1.0;
   const double norm = inv * sqrt(total);
@@ -219,13 +210,6 @@ __global__ __launch_bounds__(THREADS) void apply_kernel(Table t, ApplyArgs a) {
   }
 }
 
-inline bool bad_ptr(const void* p) { return !p || ((uintptr_t)p & 3); }
-
-inline int launched() {
-  const hipError_t err = hipGetLastError();
-  return err == hipSuccess ? 0 : (int)err;
-}
-
 inline int64_t chunks_of(int64_t numel) { return (numel + CHUNK - 1) / CHUNK; }
 
 }  // namespace
@@ -251,18 +235,18 @@ extern "C" int cgvp_optim_adam_step(const cgvp_optim_segment* segs, int32_t num_
   const cgvp_optim_hyper& h = *hyper;
   if (!(h.beta1 >= 0.0 && h.beta1 < 1.0) || !(h.beta2 >= 0.0 && h.beta2 < 1.0) || !(h.eps >= 0.0) || h.growth_interval < 1)
     return CGVP_ERR_BAD_ARG;
-  if (bad_ptr(lr) || bad_ptr(step) || bad_ptr(grad_norm) || bad_ptr(found_inf)) return CGVP_ERR_BAD_ARG;
-  if ((scale == nullptr) != (growth_tracker == nullptr) || (scale && (bad_ptr(scale) || bad_ptr(growth_tracker)))) return CGVP_ERR_BAD_ARG;
+  if (bad_ptr(lr, 4) || bad_ptr(step, 4) || bad_ptr(grad_norm, 4) || bad_ptr(found_inf, 4)) return CGVP_ERR_BAD_ARG;
+  if ((scale == nullptr) != (growth_tracker == nullptr) || (scale && (bad_ptr(scale, 4) || bad_ptr(growth_tracker, 4)))) return CGVP_ERR_BAD_ARG;
   int64_t chunks = 0;
   for (int32_t i = 0; i < num_segments; ++i) {
     const cgvp_optim_segment& s = segs[i];
     if (s.numel < 0) return CGVP_ERR_BAD_ARG;
     if (s.numel == 0) continue;
-    if (bad_ptr(s.param) || bad_ptr(s.grad) || bad_ptr(s.exp_avg) || bad_ptr(s.exp_avg_sq)) return CGVP_ERR_BAD_ARG;
+    if (bad_ptr(s.param, 4) || bad_ptr(s.grad, 4) || bad_ptr(s.exp_avg, 4) || bad_ptr(s.exp_avg_sq, 4)) return CGVP_ERR_BAD_ARG;
     chunks += chunks_of(s.numel);
     if (chunks > 0x7fffffffll) return CGVP_ERR_BAD_ARG;
   }
-  if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < kPartials + 8 * chunks) return CGVP_ERR_BAD_ARG;
+  if (bad_ptr(workspace, 8) || workspace_bytes < kPartials + 8 * chunks) return CGVP_ERR_BAD_ARG;
 
   hipStream_t st = (hipStream_t)stream;
   StepFactors* factors = static_cast<StepFactors*>(workspace);
@@ -283,9 +267,9 @@ extern "C" int cgvp_optim_adam_step(const cgvp_optim_segment* segs, int32_t num_
       }
       if (t.count == CAP || (i == num_segments && t.count > 0)) {
         const unsigned grid = (unsigned)t.first[t.count];
-        if (pass == 0) hipLaunchKernelGGL(norm_kernel, dim3(grid), dim3(THREADS), 0, st, t, partial + base);
-        else hipLaunchKernelGGL(apply_kernel, dim3(grid), dim3(THREADS), 0, st, t, apply);
-        if (const int rc = launched()) return rc;
+        if (pass == 0) launch<norm_kernel>(dim3(grid), dim3(THREADS), 0, st, t, partial + base);
+        else launch<apply_kernel>(dim3(grid), dim3(THREADS), 0, st, t, apply);
+        if (const int rc = launch_status()) return rc;
         base += grid;
         t.count = 0;
       }
@@ -294,8 +278,8 @@ extern "C" int cgvp_optim_adam_step(const cgvp_optim_segment* segs, int32_t num_
       const FinishArgs f{partial, chunks, factors, lr, step, scale, growth_tracker, grad_norm, found_inf,
                          h.beta1, h.beta2, h.weight_decay, h.max_norm, h.growth_factor, h.backoff_factor,
                          h.growth_interval, h.dry ? 1 : 0};
-      hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(THREADS), 0, st, f);
-      if (const int rc = launched()) return rc;
+      launch<finish_kernel>(dim3(1), dim3(THREADS), 0, st, f);
+      if (const int rc = launch_status()) return rc;
     }
   }
   return 0;

@@ -57,10 +57,6 @@ inline bool gine_recompute() {
 }
 inline int num_convs_of(const cgvp_layout& l) { return l.conv_stride > 0 ? (l.ln_out - l.conv0) / l.conv_stride : 0; }
 inline int esize(const cgvp_dims* d) { return d->storage == CGVP_BF16 ? 2 : 4; }
-inline int launch_status() {
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
-}
 template <typename T>
 inline T* at(void* base, int64_t off) { return reinterpret_cast<T*>(reinterpret_cast<char*>(base) + off); }
 template <typename T>
@@ -191,7 +187,7 @@ int cgvp_stage_buffers(const cgvp_stage_item* items, int32_t n, void* stream) {
   }
   int64_t blocks = (most / 16 + 255) / 256;            // one uint4 per thread on the largest item; smaller items finish early
   blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
-  hipLaunchKernelGGL(stage_kernel, dim3((unsigned)blocks, (unsigned)n), dim3(256), 0, (hipStream_t)stream, t);
+  launch<stage_kernel>(dim3((unsigned)blocks, (unsigned)n), dim3(256), 0, (hipStream_t)stream, t);
   return launch_status();
 }
 

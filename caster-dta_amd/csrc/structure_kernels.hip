@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "../../include/caster_gvp_structure.h"
+#include "gvp_host.h"
 
 namespace {
 
@@ -207,11 +208,6 @@ inline bool grid_for(int64_t items, int per_block, unsigned& blocks) {
   return true;
 }
 
-inline int launched() {
-  const hipError_t err = hipGetLastError();
-  return err == hipSuccess ? 0 : (int)err;
-}
-
 }  // namespace
 
 extern "C" int cgvp_structure_version(void) { return CGVP_STRUCTURE_VERSION; }
@@ -225,8 +221,8 @@ extern "C" int cgvp_node_featurise(const float* coords, const int64_t* types, co
   unsigned blocks;
   if (!coords || !ptr || !x_s || !x_v || num_graphs < 1 || !grid_for(num_nodes, 256, blocks)) return CGVP_ERR_BAD_ARG;
   NodeArgs a{coords, types, ptr, props, num_nodes, num_graphs, num_types, num_props, x_s, x_v, batch, seq};
-  hipLaunchKernelGGL(node_feat_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
-  return launched();
+  launch<node_feat_kernel>(dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+  return launch_status();
 }
 
 extern "C" int cgvp_radius_graph_count(const float* ca_xyz, const int64_t* ptr, int64_t num_nodes, int64_t num_graphs,
@@ -238,8 +234,8 @@ extern "C" int cgvp_radius_graph_count(const float* ca_xyz, const int64_t* ptr, 
   EdgeArgs a{};
   a.ca = ca_xyz; a.ptr = ptr; a.N = num_nodes; a.B = num_graphs; a.r2 = radius * radius; a.keep_self = keep_self_loops != 0;
   a.deg = deg;
-  hipLaunchKernelGGL(radius_count_kernel, dim3(blocks), dim3(WAVE * WAVES_PER_BLOCK), 0, (hipStream_t)stream, a);
-  return launched();
+  launch<radius_count_kernel>(dim3(blocks), dim3(WAVE * WAVES_PER_BLOCK), 0, (hipStream_t)stream, a);
+  return launch_status();
 }
 
 extern "C" int cgvp_knn_graph_select(const float* ca_xyz, const int64_t* ptr, int64_t num_nodes, int64_t num_graphs,
@@ -253,8 +249,8 @@ extern "C" int cgvp_knn_graph_select(const float* ca_xyz, const int64_t* ptr, in
   EdgeArgs a{};
   a.ca = ca_xyz; a.ptr = ptr; a.N = num_nodes; a.B = num_graphs; a.k = k; a.keep_self = keep_self_loops != 0;
   a.tau_d2 = tau_d2; a.tau_j = tau_j; a.deg = deg;
-  hipLaunchKernelGGL(knn_select_kernel, dim3(blocks), dim3(WAVE * WAVES_PER_BLOCK), 0, (hipStream_t)stream, a);
-  return launched();
+  launch<knn_select_kernel>(dim3(blocks), dim3(WAVE * WAVES_PER_BLOCK), 0, (hipStream_t)stream, a);
+  return launch_status();
 }
 
 extern "C" int cgvp_graph_fill(const float* ca_xyz, const int64_t* ptr, int64_t num_nodes, int64_t num_graphs,
@@ -269,6 +265,6 @@ extern "C" int cgvp_graph_fill(const float* ca_xyz, const int64_t* ptr, int64_t 
   EdgeArgs a{};
   a.ca = ca_xyz; a.ptr = ptr; a.N = num_nodes; a.B = num_graphs; a.r2 = radius * radius; a.keep_self = keep_self_loops != 0;
   a.tau_d2_in = tau_d2; a.tau_j_in = tau_j; a.rowstart = rowstart; a.E = num_edges; a.ei = edge_index;
-  hipLaunchKernelGGL(graph_fill_kernel, dim3(blocks), dim3(WAVE * WAVES_PER_BLOCK), 0, (hipStream_t)stream, a);
-  return launched();
+  launch<graph_fill_kernel>(dim3(blocks), dim3(WAVE * WAVES_PER_BLOCK), 0, (hipStream_t)stream, a);
+  return launch_status();
 }

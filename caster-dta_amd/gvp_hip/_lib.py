@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-import torch  # noqa: F401  (must be imported first: its libamdhip64.so.7 is the HIP runtime we bind to)
+import torch  # (must be imported first: its libamdhip64.so.7 is the HIP runtime we bind to)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # CGVP_LIB_PATH: A/B builds of the same ABI (diagnostics); the default is the in-tree library
@@ -235,6 +235,24 @@ def exported_symbols():
     return tuple(_SIGNATURES)
 
 
+def bind(handle, signatures, version_symbol=None, expected=None, what=None):
+    """`handle` with the entry points of one header typed: `signatures` maps a name to (restype, argtypes).  With a
+    `version_symbol`, the number it returns must be `expected` (`what` names it in the error: "ABI", "metrics
+    version").  The opt-in headers (optim, metrics, structure) keep a table of their own and bind it here on the
+    handle of `lib()`."""
+    for name, (res, args) in signatures.items():
+        try:
+            fn = getattr(handle, name)
+        except AttributeError as e:
+            raise HipLibraryError(f"{LIB_PATH} does not export {name}; rebuild the library") from e
+        fn.restype, fn.argtypes = res, args
+    if version_symbol is not None:
+        have = getattr(handle, version_symbol)()
+        if have != expected:
+            raise HipLibraryError(f"{LIB_PATH} has {what} {have}, binding expects {expected}")
+    return handle
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -246,16 +264,22 @@ def lib():
             handle = C.CDLL(LIB_PATH)
         except OSError as e:  # pragma: no cover
             raise HipLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-        for name, (res, args) in _SIGNATURES.items():
-            try:
-                fn = getattr(handle, name)
-            except AttributeError as e:
-                raise HipLibraryError(f"{LIB_PATH} does not export {name}; rebuild the library") from e
-            fn.restype, fn.argtypes = res, args
-        if handle.cgvp_abi_version() != ABI_VERSION:
-            raise HipLibraryError(f"{LIB_PATH} has ABI {handle.cgvp_abi_version()}, binding expects {ABI_VERSION}")
-        _lib = handle
+        _lib = bind(handle, _SIGNATURES, "cgvp_abi_version", ABI_VERSION, "ABI")
     return _lib
+
+
+# ---- what every binding module passes to the C ABI, and the check in front of it
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else C.c_void_p(0)
+
+
+def _on_gpu(t, name, note="; there is no CPU path"):
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: caster-dta_amd runs on MI355X only (got a {t.device} tensor){note}")
 
 
 _bridge = False

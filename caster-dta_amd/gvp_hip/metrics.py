@@ -11,11 +11,13 @@ concordance index, the last one a Python double loop over all pairs) as one call
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 
 import torch
 
 from . import _lib
+from ._lib import _on_gpu, _ptr, _stream
 
 METRICS_VERSION = 1      # CGVP_METRICS_VERSION
 TILE = 256               # CGVP_METRICS_TILE
@@ -30,7 +32,6 @@ _SIGNATURES = {
     "cgvp_metrics_workspace_bytes": (C.c_int64, [_I64]),
     "cgvp_metrics_compute": (C.c_int, [_P, _P, _P, _I64, _P, _P, _P, _I64, _P]),
 }
-_bound = None
 
 
 def exported_symbols():
@@ -38,22 +39,10 @@ def exported_symbols():
     return tuple(_SIGNATURES)
 
 
+@functools.lru_cache(maxsize=None)
 def lib():
-    """libcaster_gvp.so (the handle of `_lib.lib()`) with the metrics entry points typed."""
-    global _bound
-    if _bound is None:
-        handle = _lib.lib()
-        for name, (res, args) in _SIGNATURES.items():
-            try:
-                fn = getattr(handle, name)
-            except AttributeError as e:
-                raise _lib.HipLibraryError(f"{_lib.LIB_PATH} does not export {name}; rebuild the library") from e
-            fn.restype, fn.argtypes = res, args
-        if handle.cgvp_metrics_version() != METRICS_VERSION:
-            raise _lib.HipLibraryError(f"{_lib.LIB_PATH} has metrics version {handle.cgvp_metrics_version()}, "
-                                       f"binding expects {METRICS_VERSION}")
-        _bound = handle
-    return _bound
+    """libcaster_gvp.so (the handle of `_lib.lib()`) with the metrics entry points typed (once)."""
+    return _lib.bind(_lib.lib(), _SIGNATURES, "cgvp_metrics_version", METRICS_VERSION, "metrics version")
 
 
 def workspace_bytes(max_rows):
@@ -64,20 +53,11 @@ def workspace_bytes(max_rows):
     return n
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else C.c_void_p(0)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _rows(t, name):
     """`t` as a flat contiguous float32 tensor (bf16 / fp16 / fp64 are cast by torch)."""
     if not isinstance(t, torch.Tensor):
         raise ValueError(f"{name}: expected a tensor")
-    if not t.is_cuda:
-        raise RuntimeError(f"{name}: caster-dta_amd runs on MI355X only (got a {t.device} tensor); there is no CPU path")
+    _on_gpu(t, name)
     if not t.dtype.is_floating_point:
         raise ValueError(f"{name}: expected a floating-point tensor, got dtype {t.dtype}")
     return t.detach().reshape(-1).to(torch.float32).contiguous()

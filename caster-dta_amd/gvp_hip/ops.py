@@ -12,6 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import Dims, GineW, Layout, Rng
+from ._lib import _on_gpu, _ptr, _stream  # noqa: F401  (defined once, there; the other op modules and the tests take them from here)
 
 CASTER_DIMS = dict(node_in_s=17, node_in_v=3, edge_in_s=32, edge_in_v=1, hidden_s=16, hidden_v=4,
                    edge_hidden_s=32, edge_hidden_v=1, out_s=64, storage=0, layer_kind=0)
@@ -19,19 +20,6 @@ LAYER_GATED, LAYER_GVPDEF, LAYER_LINEAR = 0, 1, 2   # cgvp_dims.layer_kind (incl
 F32, BF16 = 0, 1   # cgvp_dims.storage: element type of the activation buffers ("bf16 storage / fp32 accumulate")
 ROW = 28  # merged node row: 16 scalars + 4x3 vector channels
 EROW = 36  # stored edge embedding row (CGVP_EDGE_ROW): 32 scalars + 1x3 vector + pad, sorted-edge order
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else C.c_void_p(0)
-
-
-def _on_gpu(t, name, note="; there is no CPU path"):
-    if not t.is_cuda:
-        raise RuntimeError(f"{name}: caster-dta_amd runs on MI355X only (got a {t.device} tensor){note}")
 
 
 def _f32(t, name):

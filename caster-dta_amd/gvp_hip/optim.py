@@ -10,10 +10,12 @@ and never synchronises: it can be captured (gvp_hip.graphed.GraphedTrainStep(opt
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import torch
 
 from . import _lib
+from ._lib import _on_gpu, _ptr, _stream
 
 OPTIM_VERSION = 1        # CGVP_OPTIM_VERSION
 MAX_SEGMENTS = 80        # CGVP_OPTIM_MAX_SEGMENTS (per launch; a step takes any number)
@@ -39,7 +41,6 @@ _SIGNATURES = {
     "cgvp_optim_workspace_bytes": (C.c_int64, [C.POINTER(C.c_int64), _I32]),
     "cgvp_optim_adam_step": (C.c_int, [C.POINTER(Segment), _I32, C.POINTER(Hyper), _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
 }
-_bound = None
 
 
 def exported_symbols():
@@ -47,22 +48,10 @@ def exported_symbols():
     return tuple(_SIGNATURES)
 
 
+@functools.lru_cache(maxsize=None)
 def lib():
-    """libcaster_gvp.so (the handle of `_lib.lib()`) with the optimizer entry points typed."""
-    global _bound
-    if _bound is None:
-        handle = _lib.lib()
-        for name, (res, args) in _SIGNATURES.items():
-            try:
-                fn = getattr(handle, name)
-            except AttributeError as e:
-                raise _lib.HipLibraryError(f"{_lib.LIB_PATH} does not export {name}; rebuild the library") from e
-            fn.restype, fn.argtypes = res, args
-        if handle.cgvp_optim_version() != OPTIM_VERSION:
-            raise _lib.HipLibraryError(f"{_lib.LIB_PATH} has optimizer version {handle.cgvp_optim_version()}, "
-                                       f"binding expects {OPTIM_VERSION}")
-        _bound = handle
-    return _bound
+    """libcaster_gvp.so (the handle of `_lib.lib()`) with the optimizer entry points typed (once)."""
+    return _lib.bind(_lib.lib(), _SIGNATURES, "cgvp_optim_version", OPTIM_VERSION, "optimizer version")
 
 
 def workspace_bytes(numels):
@@ -115,9 +104,7 @@ class FusedAdam(torch.optim.Optimizer):
         for i, p in enumerate(ps):
             if p.dtype != torch.float32:
                 raise ValueError(f"FusedAdam: parameter {i} is {p.dtype}; only float32 parameters are updated")
-            if not p.is_cuda:
-                raise RuntimeError(f"FusedAdam: parameter {i} is a {p.device} tensor; caster-dta_amd runs on MI355X only, "
-                                   "there is no CPU path")
+            _on_gpu(p, f"FusedAdam: parameter {i}")
             if p.device != ps[0].device:
                 raise ValueError(f"FusedAdam: parameter {i} is on {p.device}, parameter 0 on {ps[0].device}")
             if not p.is_contiguous():
@@ -257,12 +244,10 @@ class FusedAdam(torch.optim.Optimizer):
                                  "parameters' device")
             hyper.growth_factor, hyper.backoff_factor = scaler.get_growth_factor(), scaler.get_backoff_factor()
             hyper.growth_interval = scaler.get_growth_interval()
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
         with torch.cuda.device(self.device):
-            rc = self._lib.cgvp_optim_adam_step(table, n, C.byref(hyper), ptr(self._lr), ptr(self._step), ptr(scale),
-                                                ptr(tracker), ptr(self._grad_norm), ptr(self._found_inf),
-                                                ptr(self._workspace), self._workspace.numel() * 8,
-                                                C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            rc = self._lib.cgvp_optim_adam_step(table, n, C.byref(hyper), _ptr(self._lr), _ptr(self._step), _ptr(scale),
+                                                _ptr(tracker), _ptr(self._grad_norm), _ptr(self._found_inf),
+                                                _ptr(self._workspace), self._workspace.numel() * 8, _stream())
         _lib.check(rc, "cgvp_optim_adam_step")
 
     def step(self, scaler=None, closure=None):

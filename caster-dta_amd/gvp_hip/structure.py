@@ -8,10 +8,12 @@ module's.  `protein_graphs` replaces the reference's per-protein CPU featuriser
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import torch
 
 from . import _lib
+from ._lib import _on_gpu, _ptr, _stream
 
 STRUCTURE_VERSION = 1    # CGVP_STRUCTURE_VERSION
 KNN_MAX = 64             # CGVP_KNN_MAX
@@ -24,7 +26,6 @@ _SIGNATURES = {
     "cgvp_knn_graph_select": (C.c_int, [_P, _P, _I64, _I64, _I32, _I32, _P, _P, _P, _P]),
     "cgvp_graph_fill": (C.c_int, [_P, _P, _I64, _I64, _F64, _P, _P, _I32, _P, _I64, _P, _P]),
 }
-_bound = None
 
 
 def exported_symbols():
@@ -32,37 +33,16 @@ def exported_symbols():
     return tuple(_SIGNATURES)
 
 
+@functools.lru_cache(maxsize=None)
 def lib():
-    """libcaster_gvp.so (the handle of `_lib.lib()`) with the structure entry points typed."""
-    global _bound
-    if _bound is None:
-        handle = _lib.lib()
-        for name, (res, args) in _SIGNATURES.items():
-            try:
-                fn = getattr(handle, name)
-            except AttributeError as e:
-                raise _lib.HipLibraryError(f"{_lib.LIB_PATH} does not export {name}; rebuild the library") from e
-            fn.restype, fn.argtypes = res, args
-        if handle.cgvp_structure_version() != STRUCTURE_VERSION:
-            raise _lib.HipLibraryError(f"{_lib.LIB_PATH} has structure version {handle.cgvp_structure_version()}, "
-                                       f"binding expects {STRUCTURE_VERSION}")
-        _bound = handle
-    return _bound
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else C.c_void_p(0)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    """libcaster_gvp.so (the handle of `_lib.lib()`) with the structure entry points typed (once)."""
+    return _lib.bind(_lib.lib(), _SIGNATURES, "cgvp_structure_version", STRUCTURE_VERSION, "structure version")
 
 
 def _checked(t, name, dtypes, what):
     if not isinstance(t, torch.Tensor):
         raise ValueError(f"{name}: expected a tensor ({what})")
-    if not t.is_cuda:
-        raise RuntimeError(f"{name}: caster-dta_amd runs on MI355X only (got a {t.device} tensor); there is no CPU path")
+    _on_gpu(t, name)
     if t.dtype not in dtypes:
         raise ValueError(f"{name}: expected {what}, got dtype {t.dtype}")
     return t.detach().contiguous()

@@ -417,6 +417,64 @@ def test_misaligned_views_between_canaries_and_two_calls_bitwise_equal(name):
     assert raw.state() == [0, 0]                                       # not passed, not touched
 
 
+def _workgroup_sum(acc):
+    """The fixed-order workgroup sum of csrc/gvp_block_sum.h over the last axis (256 threads) in float64: the 64 lanes
+    of each wave by halving (acc[l] += acc[l + off], off = 32 .. 1), then the waves 0, 1, 2, 3."""
+    lanes = acc.reshape(acc.shape[:-1] + (4, 64)).copy()
+    off = 32
+    while off:
+        lanes[..., :off] = lanes[..., :off] + lanes[..., off:2 * off]
+        off >>= 1
+    total = lanes[..., 0, 0].copy()
+    for w in range(1, 4):
+        total = total + lanes[..., w, 0]
+    return total
+
+
+def ordered_mean(rows):
+    """The mean of float32 `rows` as moments1_kernel and means_kernel form it, addition by addition: inside a chunk of
+    CH rows thread t adds rows base + k * 256 + t, k = 0 .. CH / 256 - 1, then the workgroup sum; across the chunks
+    thread t adds the partials t, t + 256, ..., then the workgroup sum; last the division by n.  Rows and partials that
+    do not exist are skipped on the device and added as +0.0 here, which leaves an accumulator that began as +0.0
+    bitwise as it was."""
+    x = np.asarray(rows, dtype=np.float32).astype(np.float64)
+    n = x.size
+    chunks = -(-n // CH)
+    x = np.concatenate([x, np.zeros(chunks * CH - n)]).reshape(chunks, CH // 256, 256)
+    acc = np.zeros((chunks, 256))
+    for k in range(CH // 256):
+        acc = acc + x[:, k, :]
+    partial = _workgroup_sum(acc)
+    partial = np.concatenate([partial, np.zeros(-chunks % 256)]).reshape(-1, 256)
+    acc = np.zeros(256)
+    for r in range(partial.shape[0]):
+        acc = acc + partial[r]
+    return float(_workgroup_sum(acc) / np.float64(n))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [256, 2048, 1 << 19])
+def test_the_two_means_are_bitwise_the_documented_order_of_additions(n):
+    """out_vals[4] and out_vals[5] (mean_pred, mean_target; the module drops them) against `ordered_mean`, bit for bit:
+    one partly filled chunk, two chunks, and 512 chunks of which every thread of means_kernel owns two.  n is a power
+    of two: the division is exact.
+
+    The inputs are randn * 10^uniform(-6, 6).  A float32 has 24 significant bits, so float64 sums of n values within D
+    decades of each other are exact, in any order, while 24 + 3.32 D + log2(n) <= 53: at n = 256 six decades show
+    nothing, twelve do.  That another order of the same additions has other bits is asserted first, on the host alone,
+    with np.sum as the other order; the seed is one for which that holds at all three sizes (of the seeds 0 .. 39 it
+    holds for 15 at n = 256 and for 23 at n = 2048)."""
+    rng = np.random.default_rng(3)
+    p, t = ((rng.standard_normal(n) * 10.0 ** rng.uniform(-6.0, 6.0, n)).astype(np.float32) for _ in range(2))
+    want = [ordered_mean(p), ordered_mean(t)]
+    for rows, mean in zip((p, t), want):
+        assert bits(mean) != bits(rows.astype(np.float64).sum() / n), "the inputs do not tell one order from another"
+    _, words = Raw(p, t).compute()
+    got = [struct.pack("<q", w) for w in words[8:10]]
+    print(f"n={n} mean_pred {got[0].hex()} want {bits(want[0]).hex()}  mean_target {got[1].hex()} want {bits(want[1]).hex()}")
+    assert got == [bits(m) for m in want]
+
+
 @pytest.mark.gpu
 def test_rows_behind_the_device_count_are_never_looked_at():
     """Buffers of capacity 2T+1 hold T+1 rows: the results are those of the T+1 rows alone, whatever lies behind."""
