@@ -1,0 +1,249 @@
+// attn_score_kernels.hip -- per-node attention scores of the varlen cross attention
+// (include/caster_gvp_attnscore.h; opt-in).
+//
+// The reference's evaluation keeps, of nn.MultiheadAttention's head-averaged weights w[b][q][k], only the column mean
+// and the column maximum of every pair (inference/evaluation.py:54-66, 97-102).  Through cgvp_attn_weights that costs a
+// host read of the longest protein / molecule, two zero-filled dense [B, Lq_max, Lk_max] tensors and a Python loop over
+// the pairs.  Here, per key row k of pair b,
+//
+//     w[q][k] = (1/H) sum_h exp(scale Q_h[q] . K_h[k] - lse[q][h]),   mean[k] = (1/nq_b) sum_q w[q][k],   max[k] = max_q w[q][k]
+//
+// goes from the compact rows to two compact [Nk] vectors in one launch for both directions.
+//
+// Work unit: one workgroup per 16-key tile of one pair, ALL heads (the maximum is taken after the head average, so a
+// wave needs every head of a weight before it can reduce it).  Keys sit on the lanes, the orientation of the d K / d V
+// kernel of attn_kernels.hip:
+//     S[q][key] = D[m = q][n = key]:  A = Qs rows (lane (m = q, g): float4 of dims 4g..4g+3), B = K rows
+// so lane (n = key, g) holds the scores of its key for the queries qb + 4g + r, r = 0..3, and accumulates their sum and
+// maximum in two registers.  K of all heads stays in registers across the query loop (4 H VGPRs).  The WPB waves of the
+// workgroup take the pair's query tiles round robin (an atom-key tile of a long protein walks hundreds of them); two
+// xor-shuffles join the four lane groups of a wave, LDS joins the waves in wave order.  No atomics: the order of every
+// sum is fixed by the shape alone.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <type_traits>
+
+#include "../../include/caster_gvp_attnscore.h"
+#include "gvp_host.h"
+
+namespace {
+
+typedef float f4 __attribute__((ext_vector_type(4)));
+constexpr int WAVE = 64, TILE = 16, HD = 16, WPB = 8, TPB = WAVE * WPB, MAX_H = CGVP_ATTN_SCORE_MAX_HEADS;
+
+__device__ __forceinline__ f4 mfma(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+// exp through v_exp_f32, as in attn_kernels.hip (the lse was produced with the same function)
+__device__ __forceinline__ float fexp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
+__device__ __forceinline__ float quad_max(float x) {
+  x = fmaxf(x, __shfl_xor(x, 16));
+  return fmaxf(x, __shfl_xor(x, 32));
+}
+__device__ __forceinline__ float quad_sum(float x) {
+  x += __shfl_xor(x, 16);
+  return x + __shfl_xor(x, 32);
+}
+
+struct Prob {
+  const float* q; const float* k; const float* lse;       // [Nq][E], [Nk][E], [Nq][H]
+  const int64_t* q_ptr; const int64_t* k_ptr;             // [B + 1]
+  float* out_mean; float* out_max;                         // [Nk]
+  int32_t units;                                           // upper bound of the key tiles: ceil(Nk / 16) + B
+};
+struct Args { Prob p[2]; int nprob; int B; float scale; };
+
+// Which pair owns tile `t` when every pair b contributes ceil((ptr[b+1] - ptr[b]) / 16) consecutive tiles?  The scan of
+// attn_kernels.hip (file-local there): wave-parallel over the pairs, 64 at a time, any B.  Returns false past the last
+// tile.  All lanes return the same (b, first row of the tile, end row of the pair).
+__device__ __forceinline__ bool locate(const int64_t* __restrict__ ptr, int B, int t, int lane, int& b, int64_t& row0,
+                                       int64_t& row_end) {
+  int base = 0;
+  for (int c = 0; c < B; c += WAVE) {
+    const int i = c + lane;
+    const int64_t lo = i < B ? ptr[i] : 0, hi = i < B ? ptr[i + 1] : 0;
+    const int tiles = (int)((hi - lo + TILE - 1) / TILE);
+    int incl = tiles;
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) {
+      const int y = __shfl_up(incl, d);
+      if (lane >= d) incl += y;
+    }
+    const int total = __shfl(incl, WAVE - 1);
+    if (t < base + total) {
+      const bool mine = t >= base + incl - tiles && t < base + incl;
+      const unsigned long long vote = __ballot(mine);
+      const int src = __ffsll((long long)vote) - 1;
+      b = c + src;
+      const int first = __shfl(base + incl - tiles, src);
+      const int64_t plo = __shfl((long long)lo, src), phi = __shfl((long long)hi, src);
+      row0 = plo + (int64_t)(t - first) * TILE;
+      row_end = phi;
+      return true;
+    }
+    base += total;
+  }
+  return false;
+}
+
+// by value, selected with a workgroup-uniform index (see attn_kernels.hip: a reference into the argument segment turned
+// every pointer use inside the loop into a vector load)
+__device__ __forceinline__ Prob pick(const Args& a, int pi) { return pi ? a.p[1] : a.p[0]; }
+__device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
+
+template <int H>
+__global__ __launch_bounds__(TPB) void attn_node_scores_kernel(Args a) {
+  __shared__ float2 part[WPB][TILE];                              // per wave and key: H x {sum, max} of w over the wave's queries
+  const int lane = threadIdx.x & 63, n = lane & 15, g = lane >> 4, wv = wave_id();
+  int64_t t = blockIdx.x;
+  int pi = 0;
+  if (t >= a.p[0].units) { t -= a.p[0].units; pi = 1; }
+  if (pi >= a.nprob) return;                                      // (every exit up to the barrier is workgroup-uniform)
+  const Prob P = pick(a, pi);
+  if (t >= P.units) return;
+  int b;
+  int64_t kt0_, k_end_;
+  if (!locate(P.k_ptr, a.B, (int)t, lane, b, kt0_, k_end_)) return;
+  // rows and element offsets in 32 bits (the host checks rows x E < 2^31), see attn_kernels.hip
+  const int kt0 = (int)kt0_, k_end = (int)k_end_;
+  const int q0 = (int)P.q_ptr[b], q_end = (int)P.q_ptr[b + 1];
+  const int kr = kt0 + n;
+  const bool kv = kr < k_end;
+  constexpr unsigned E = H * HD;
+  float sum = 0.f, mx = 0.f;                                      // weights are >= 0: 0 is the maximum of no query
+  int qb = q0 + TILE * wv;                                        // this wave's first query tile; the stride is WPB tiles
+  if (qb < q_end) {
+    // K of every head: a lane behind the pair's last key reads that last key's row (the tile holds at least one key)
+    // and computes a finite column that is never stored
+    f4 kk[H];
+    {
+      const unsigned ko = (unsigned)(kv ? kr : k_end - 1) * E + 4 * g;
+#pragma unroll
+      for (int h = 0; h < H; ++h) kk[h] = *reinterpret_cast<const f4*>(P.k + ko + h * HD);
+    }
+    // The next query tile is loaded while the current one is computed, unconditionally, on offsets that advance per
+    // call and are clamped to the pair's last query (see attn_fwd_kernel): rows behind q_end are copies of the last
+    // query's and are zeroed in the peeled tail iteration only.
+    struct QT { f4 qa[H]; float lse[4][H]; };
+    const unsigned q_step = WPB * TILE * E, h_step = WPB * TILE * H;
+    const unsigned qo_last = (unsigned)(q_end - 1) * E + 4 * g, ho_last = (unsigned)(q_end - 1) * H;
+    unsigned qo = (unsigned)(qb + n) * E + 4 * g;                 // this lane's row as the M index of the score product
+    unsigned ho[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) ho[r] = (unsigned)(qb + 4 * g + r) * H;   // rows of D this lane holds: queries qb + 4g + r
+    auto load_tile = [&](QT& T) {
+      const unsigned qc = qo < qo_last ? qo : qo_last;
+      qo += q_step;
+#pragma unroll
+      for (int h = 0; h < H; ++h) T.qa[h] = *reinterpret_cast<const f4*>(P.q + qc + h * HD) * a.scale;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const unsigned hc = ho[r] < ho_last ? ho[r] : ho_last;
+        ho[r] += h_step;
+        if constexpr (H % 4 == 0) {
+#pragma unroll
+          for (int h = 0; h < H; h += 4) {
+            const f4 l = *reinterpret_cast<const f4*>(P.lse + hc + h);
+            T.lse[r][h] = l[0]; T.lse[r][h + 1] = l[1]; T.lse[r][h + 2] = l[2]; T.lse[r][h + 3] = l[3];
+          }
+        } else {
+#pragma unroll
+          for (int h = 0; h < H; ++h) T.lse[r][h] = P.lse[hc + h];
+        }
+      }
+    };
+    QT nxt;
+    load_tile(nxt);
+    auto tile = [&](int qt, auto tail) {
+      const QT cur = nxt;
+      load_tile(nxt);                                             // past the end: copies of the last query, never used
+      float w[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int h = 0; h < H; ++h) {
+        f4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int x = 0; x < 4; ++x) s = mfma(cur.qa[h][x], kk[h][x], s);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) w[r] += fexp(fminf(s[r] - cur.lse[r][h], 0.f));   // a probability: never above 1
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float x = w[r];
+        if constexpr (decltype(tail)::value) x = qt + 4 * g + r < q_end ? x : 0.f;
+        sum += x;
+        mx = fmaxf(mx, x);
+      }
+    };
+    for (; qb + TILE <= q_end; qb += WPB * TILE) tile(qb, std::false_type{});
+    if (qb < q_end) tile(qb, std::true_type{});                   // the pair's partial last tile belongs to one wave
+    sum = quad_sum(sum);
+    mx = quad_max(mx);
+  }
+  if (g == 0) part[wv][n] = make_float2(sum, mx);
+  __syncthreads();
+  if (wv != 0 || g != 0 || !kv) return;
+  float s = 0.f, m = 0.f;
+#pragma unroll
+  for (int i = 0; i < WPB; ++i) {                                 // wave order: fixed
+    const float2 p = part[i][n];
+    s += p.x;
+    m = fmaxf(m, p.y);
+  }
+  const float invh = 1.0f / (float)H;
+  const int nq = q_end - q0;
+  P.out_mean[kr] = nq > 0 ? s * invh / (float)nq : 0.f;
+  P.out_max[kr] = m * invh;                                       // a positive factor: commutes with the maximum
+}
+
+template <int H>
+int launch_scores(unsigned grid, hipStream_t st, const Args& a) {
+  return launch<attn_node_scores_kernel<H>>(dim3(grid), dim3(TPB), 0, st, a);
+}
+
+}  // namespace
+
+extern "C" int cgvp_attn_score_version(void) { return CGVP_ATTN_SCORE_VERSION; }
+
+extern "C" int cgvp_attn_node_scores(const cgvp_attn_score_problem* probs, int32_t num_problems, int64_t num_pairs,
+                                     int32_t heads, float scale, void* stream) {
+  if (!probs || num_problems < 1 || num_problems > 2 || num_pairs < 0 || num_pairs >= ((int64_t)1 << 30) || heads < 1)
+    return CGVP_ERR_BAD_ARG;
+  if (heads > MAX_H) return CGVP_ERR_UNSUPPORTED_DIMS;
+  Args a;
+  a.nprob = num_problems; a.B = (int)num_pairs; a.scale = scale;
+  // the problem whose key tiles walk the most queries gets the low workgroup indices (they start first), as the
+  // d K / d V launch of cgvp_attn_bwd orders its two
+  const bool swap = num_problems == 2 && probs[1].num_q > probs[0].num_q;
+  const uintptr_t lse_align = heads % 4 == 0 ? 15 : 3;
+  for (int i = 0; i < 2; ++i) {
+    Prob& p = a.p[i];
+    p = Prob{};
+    if (i >= num_problems) continue;
+    const cgvp_attn_score_problem& s = probs[swap ? 1 - i : i];
+    if (s.num_q < 0 || s.num_k < 0 || !s.q_ptr || !s.k_ptr) return CGVP_ERR_BAD_ARG;
+    if ((s.num_q + TILE) * (int64_t)(heads * HD) >= ((int64_t)1 << 31) || (s.num_k + TILE) * (int64_t)(heads * HD) >= ((int64_t)1 << 31))
+      return CGVP_ERR_BAD_ARG;                             // the kernel addresses rows with 32-bit element offsets
+    if (s.num_q > 0 && (!s.q || !s.lse)) return CGVP_ERR_BAD_ARG;
+    if (s.num_k > 0 && (!s.k || !s.out_mean || !s.out_max)) return CGVP_ERR_BAD_ARG;
+    if (((uintptr_t)s.q & 15) || ((uintptr_t)s.k & 15) || ((uintptr_t)s.lse & lse_align)) return CGVP_ERR_BAD_ARG;
+    if ((((uintptr_t)s.out_mean | (uintptr_t)s.out_max) & 3) || (((uintptr_t)s.q_ptr | (uintptr_t)s.k_ptr) & 7)) return CGVP_ERR_BAD_ARG;
+    p.q = s.q; p.k = s.k; p.lse = s.lse; p.q_ptr = s.q_ptr; p.k_ptr = s.k_ptr;
+    p.out_mean = s.out_mean; p.out_max = s.out_max;
+    p.units = (int32_t)((s.num_k + TILE - 1) / TILE + num_pairs);
+  }
+  if (num_pairs == 0) return 0;
+  const unsigned grid = (unsigned)((int64_t)a.p[0].units + a.p[1].units);
+  hipStream_t st = (hipStream_t)stream;
+  int rc = 0;
+  switch (heads) {
+    case 1: rc = launch_scores<1>(grid, st, a); break;
+    case 2: rc = launch_scores<2>(grid, st, a); break;
+    case 3: rc = launch_scores<3>(grid, st, a); break;
+    case 4: rc = launch_scores<4>(grid, st, a); break;
+    case 5: rc = launch_scores<5>(grid, st, a); break;
+    case 6: rc = launch_scores<6>(grid, st, a); break;
+    case 7: rc = launch_scores<7>(grid, st, a); break;
+    default: rc = launch_scores<8>(grid, st, a); break;
+  }
+  if (rc) return rc;
+  return launch_status();
+}

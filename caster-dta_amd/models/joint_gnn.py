@@ -22,6 +22,7 @@ xGMI) right before `pm_embed_lin` (joint_gnn.py:272-273); the affinity head then
 runs replicated and every rank returns all B predictions.  Training adds ONE flat
 all-reduce of the pre-gather parameter gradients (`reduce_pair_parallel_grads`).
 """
+from collections import namedtuple
 from functools import partial
 
 import contextlib
@@ -50,6 +51,26 @@ def to_dense_batch(x, batch=None, batch_size=None):
     mask = torch.zeros(batch_size * lmax, dtype=torch.bool, device=x.device)
     mask[slot] = True
     return dense.view(batch_size, lmax, x.shape[1]), mask.view(batch_size, lmax)
+
+
+# Per-node attention scores of one cross-attention layer, compact (one value per residue [N] / per atom [Na]): the column
+# mean and column max of the pair's head-averaged weight matrices, what inference/evaluation.py:97-102 keeps of them as
+# protein_attention, max_protein_attention (reduced over the pair's atom queries) and molecule_attention,
+# max_molecule_attention (reduced over its residue queries).
+NodeAttention = namedtuple("NodeAttention", ["residue_mean", "residue_max", "atom_mean", "atom_max"])
+
+
+def _dense_node_attention(w1, w2, mask1, mask2):
+    """NodeAttention from one layer's dense weights w1 [B, L1, L2] (side-1 queries) / w2 [B, L2, L1] and the row masks:
+    the same four vectors the varlen kernel gives, with stock ops (the dense fallback path)."""
+    def reduce(w, qmask, kmask):
+        m = qmask.unsqueeze(-1)
+        w = w * m                                                  # rows of padding queries hold a softmax of their own
+        mean = w.sum(dim=1) / qmask.sum(dim=1, keepdim=True).clamp_min(1).to(w.dtype)
+        return mean[kmask], w.max(dim=1).values[kmask]
+    atom_mean, atom_max = reduce(w1, mask1, mask2)
+    residue_mean, residue_max = reduce(w2, mask2, mask1)
+    return NodeAttention(residue_mean, residue_max, atom_mean, atom_max)
 
 
 class _BatchNorm(nn.Module):
@@ -177,6 +198,11 @@ class JointGNN(nn.Module):
         # inference/evaluation.py:43-66 consumes), skipped in training (train_model.py:564 discards them);
         # "always" / "never" force it.  Dense [B, Rmax, Amax] / [B, Amax, Rmax] as in the reference.
         self.attention_weights = "auto"
+        # Per-node attention scores (NodeAttention per layer, in `last_node_attention` after a forward): "never" (default),
+        # "always", or "auto" = in eval mode only.  Unlike the dense weights they need no host read and no padded tensor
+        # (gvp_hip.attention_scores), so they are independent of `attention_weights` and can be on inside a captured step.
+        self.node_attention = "never"
+        self.last_node_attention = None
 
     # ------------------------------------------------------------ multi-GPU
     def enable_pair_parallel(self, group=None, pair_counts=None, always_communicate=False):
@@ -361,6 +387,11 @@ class JointGNN(nn.Module):
         with lanes.atom():
             atom = self._stack(atom, self.atom_lins, self.atom_norms, sites)
         attn = None
+        if self.node_attention not in ("never", "always", "auto"):
+            raise ValueError(f"node_attention must be 'never', 'always' or 'auto', got {self.node_attention!r}")
+        want_scores = self.cross_attn_module is not None and (
+            self.node_attention == "always" or (self.node_attention == "auto" and not self.training))
+        scores = [] if want_scores else None
         if varlen:
             # compact rows end to end: varlen cross attention (one launch for both directions) + segment pooling
             pbatch, rptr = self._offsets(protein_graph_data, pbatch, residue)
@@ -372,7 +403,8 @@ class JointGNN(nn.Module):
             lanes.fork(aptr, mbatch)
             if self.cross_attn_module is not None:
                 want = self.attention_weights == "always" or (self.attention_weights == "auto" and not self.training)
-                residue, atom, attn = self.cross_attn_module.forward_varlen(residue, atom, rptr, aptr, want, sites, lanes)
+                residue, atom, attn = self.cross_attn_module.forward_varlen(residue, atom, rptr, aptr, want, sites, lanes,
+                                                                            scores_out=scores)
             protein = self._pool_rows(residue, pbatch, rptr)
             with lanes.atom():
                 molecule = self._pool_rows(atom, mbatch, aptr)
@@ -381,7 +413,11 @@ class JointGNN(nn.Module):
             residue, rmask = to_dense_batch(residue, pbatch)
             atom, amask = to_dense_batch(atom, mbatch)
             residue, atom, attn = self.cross_attn_module(residue, atom, rmask, amask)
+            if want_scores:
+                scores = [_dense_node_attention(w1.detach(), w2.detach(), rmask, amask) for w1, w2 in attn]
             protein, molecule = self._pool(residue, rmask), self._pool(atom, amask)
+        if want_scores or self.last_node_attention is not None:
+            self.last_node_attention = scores
         if self.include_post_pool_layernorm:
             protein = self.protein_post_pool_norm(protein)
         protein = sites.act_dropout(protein, self.activation, self.dropout)
@@ -400,6 +436,23 @@ class JointGNN(nn.Module):
         z = sites.act_dropout(self.pm_embed_lin(pair), self.activation, self.dropout)
         z = self._stack(z, self.out_fc_layers, self.out_fc_norms, sites)
         return self.output_layer(z), attn
+
+    @torch.no_grad()
+    def predict_with_node_attention(self, protein_graph_data, molecule_graph_data):
+        """(affinity [B, 1], [NodeAttention per cross-attention layer]) of one batch, in eval mode under no_grad: the
+        prediction of a plain eval forward and the four per-node columns of inference/evaluation.py, compact (split them
+        per pair with gvp_hip.attention_scores.per_pair).  The dense [B, Rmax, Amax] weights are never built."""
+        if self.cross_attn_module is None:
+            raise RuntimeError("predict_with_node_attention: the model has no cross-attention layer")
+        saved = (self.training, self.node_attention, self.attention_weights)
+        self.eval()
+        self.node_attention, self.attention_weights = "always", "never"
+        try:
+            affinity, _ = self.forward(protein_graph_data, molecule_graph_data)
+            return affinity, self.last_node_attention
+        finally:
+            self.node_attention, self.attention_weights = saved[1], saved[2]
+            self.train(saved[0])
 
     @staticmethod
     def _make_lins_from_depth(depth, in_dim, scale_factor=2, include_norms=None):
@@ -512,11 +565,12 @@ class CrossAttentionModule(nn.Module):
             return k.contiguous(), v.contiguous()
         return fast_linear(x_kv, parts[4], parts[5]), fast_linear(x_kv, parts[6], parts[7])
 
-    def forward_varlen(self, embed_1, embed_2, ptr1, ptr2, need_weights=False, sites=None, lanes=None):
+    def forward_varlen(self, embed_1, embed_2, ptr1, ptr2, need_weights=False, sites=None, lanes=None, scores_out=None):
         """`forward` on compact rows: embed_1 [N1, D] with graph offsets ptr1, embed_2 [N2, D] with ptr2; every
         graph b of side 1 attends to graph b of side 2 and vice versa (joint_gnn.py:376-398).  The softmax(QK^T)V
         core of both directions is one launch of caster_gvp::cross_attention; projections and feed-forward are
-        GEMMs on the compact rows.  Returns (embed_1, embed_2, (w1, w2) or None)."""
+        GEMMs on the compact rows.  Returns (embed_1, embed_2, (w1, w2) or None).  `scores_out`: a list this layer
+        appends its NodeAttention to (caster_gvp::cross_attention_node_scores: one launch, no host read)."""
         from gvp_hip import attention_ops  # noqa: F401  (registers the ops)
         from gvp_hip.head_ops import fast_layer_norm      # nn.LayerNorm on compact rows: one-pass kernels each way
         if lanes is None:
@@ -552,6 +606,11 @@ class CrossAttentionModule(nn.Module):
             weights = tuple(torch.ops.caster_gvp.cross_attention_weights(q1.detach(), k1.detach(), lse1.detach(),
                                                                          q2.detach(), k2.detach(), lse2.detach(),
                                                                          ptr1, ptr2, heads, l1, l2))
+        if scores_out is not None:
+            from gvp_hip import attention_scores  # noqa: F401  (registers the op)
+            atom_mean, atom_max, residue_mean, residue_max = torch.ops.caster_gvp.cross_attention_node_scores(
+                q1.detach(), k1.detach(), lse1.detach(), q2.detach(), k2.detach(), lse2.detach(), ptr1, ptr2, heads)
+            scores_out.append(NodeAttention(residue_mean, residue_max, atom_mean, atom_max))
         if self.include_residual_stream:
             if sites is None:
                 from gvp_hip.head_ops import DropSites
@@ -590,10 +649,11 @@ class StackedCrossAttentionModule(nn.Module):
     def varlen_supported(self, rows):
         return all(layer.varlen_supported(rows) for layer in self.cross_attn_layers)
 
-    def forward_varlen(self, embed_1, embed_2, ptr1, ptr2, need_weights=False, sites=None, lanes=None):
+    def forward_varlen(self, embed_1, embed_2, ptr1, ptr2, need_weights=False, sites=None, lanes=None, scores_out=None):
         weights = []
         for layer in self.cross_attn_layers:
-            embed_1, embed_2, w = layer.forward_varlen(embed_1, embed_2, ptr1, ptr2, need_weights, sites, lanes)
+            embed_1, embed_2, w = layer.forward_varlen(embed_1, embed_2, ptr1, ptr2, need_weights, sites, lanes,
+                                                       scores_out=scores_out)
             weights.append(w)
         return embed_1, embed_2, (weights if need_weights else None)
 
