@@ -24,19 +24,17 @@
 #include "gvp_internal.h"
 #include "gvp_quad.h"
 
+#ifdef CGVP_STAMPS     // diagnostic build only (tools/stamp_gine_bwd.py): clock stamps at phase boundaries, one row of 16 per wave
+namespace { __device__ unsigned long long* g_stamp_buf_gine = nullptr; }
+#endif
+#define CGVP_STAMP_BUF g_stamp_buf_gine
+#include "gvp_stamp.h"
+
 using namespace gq;
 
 namespace {
 
-constexpr int WAVE = 64, TILE = 16;
 constexpr int NTL = 4;                 // edge tiles per chunk (64 edges)
-
-constexpr int pad4i(int x) { return (x + 3) / 4 * 4; }
-
-__device__ __forceinline__ int opaque_lane(int lane) {     // see gvp_quad_bwd_kernels.hip
-  asm volatile("" : "+v"(lane));
-  return lane;
-}
 
 // P1 slots over W (a multiple of 16) channels of which only the first VALID exist.
 // Ordering of a wave's OWN LDS traffic between phases (rows written by some lanes, read by others of the same wave).
@@ -61,21 +59,6 @@ __device__ __forceinline__ int opaque_lane(int lane) {     // see gvp_quad_bwd_k
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          \
     __builtin_amdgcn_wave_barrier();                            \
   } while (0)
-#endif
-
-#ifdef CGVP_STAMPS     // diagnostic build only (tools/stamp_gine_bwd.py): s_memtime at phase boundaries, one row of 16 per wave
-__device__ unsigned long long* g_stamp_buf_gine = nullptr;
-#define GSTAMP(slot)                                                                         \
-  do {                                                                                       \
-    __builtin_amdgcn_sched_barrier(0);                                                       \
-    unsigned long long t_;                                                                   \
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory"); \
-    __builtin_amdgcn_sched_barrier(0);                                                       \
-    if (g_stamp_buf_gine && (threadIdx.x & 63) == 0)                                         \
-      g_stamp_buf_gine[((size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 16 + (slot)] = t_;   \
-  } while (0)
-#else
-#define GSTAMP(slot) do {} while (0)
 #endif
 
 template <int W, int VALID>
@@ -124,7 +107,7 @@ struct GineQ {
   static constexpr int MI = CINP / 16, MH = CHID / 16, MO = COUT / 16;
   // layer gradient block, state_dict order (= GineLay of gvp_kernels.hip)
   static constexpr int L_EPS = 0, L_W0 = 1, L_B0 = L_W0 + CHID * CIN, L_W1 = L_B0 + CHID, L_B1 = L_W1 + COUT * CHID,
-                       L_WE = L_B1 + COUT, L_BE = L_WE + CIN * KE, L_SIZE = L_BE + CIN, BLK = pad4i(L_SIZE);
+                       L_WE = L_B1 + COUT, L_BE = L_WE + CIN * KE, L_SIZE = L_BE + CIN, BLK = pad4(L_SIZE);
   typedef SegClip<CINP, CIN> KIn;
   typedef Seg<P1, 0, CHID> KHid;
   typedef Seg<P1, 0, COUT> KOut;
@@ -358,9 +341,9 @@ __global__ __launch_bounds__((WAVE * GineQ<CIN, CHID, COUT, NT, NET, ED, EG>::WP
   if constexpr (EG) stage_fragments<typename Q::GET, GQ_TPB>(frag + Q::F_ET, a.we);
   stage_biases<CIN, CINP, CHID, COUT, GQ_TPB>(frag + Q::V_BE, frag + Q::V_B0, frag + Q::V_B1, a.be, a.b0, a.b1);
   for (int k = lane0; k < Q::BLK / 4; k += WAVE) reinterpret_cast<f4*>(blk)[k] = f4{0.f, 0.f, 0.f, 0.f};
-  GSTAMP(0);
+  STAMP(0);
   __syncthreads();
-  GSTAMP(1);
+  STAMP(1);
 
   const f4 zero = {0.f, 0.f, 0.f, 0.f};
   const float eps1 = 1.0f + a.eps[0];
@@ -421,9 +404,9 @@ __global__ __launch_bounds__((WAVE * GineQ<CIN, CHID, COUT, NT, NET, ED, EG>::WP
     for (int32_t c0 = e0; !SAVED && c0 < e1; c0 += NTL * TILE) {
       const int lane = opaque_lane(lane0), i = lane & 15, g = lane >> 4;
       f4 xj[NTL][MI];
-      GSTAMP(8);
+      STAMP(8);
       load_chunk(c0, lane, xj);
-      GSTAMP(9);
+      STAMP(9);
 #pragma unroll
       for (int t = 0; t < NTL; ++t) {
         if (c0 + t * TILE >= e1) break;
@@ -449,7 +432,7 @@ __global__ __launch_bounds__((WAVE * GineQ<CIN, CHID, COUT, NT, NET, ED, EG>::WP
       }
     }
 
-    GSTAMP(2);
+    STAMP(2);
     // ---- B. the MLP of the 16 atoms, forward and backward
     {
       const int lane = opaque_lane(lane0), i = lane & 15, g = lane >> 4;
@@ -516,7 +499,7 @@ __global__ __launch_bounds__((WAVE * GineQ<CIN, CHID, COUT, NT, NET, ED, EG>::WP
         apply<typename Q::G0T, 1>(frag + Q::F_0T, mt, bdt, acc, lane);
         dh[mt] = acc[0];
       }
-      GSTAMP(3);
+      STAMP(3);
       // ---- weight gradients of the two Linear layers
       {
         f4 AT[MO], BT[MH];
@@ -565,7 +548,7 @@ __global__ __launch_bounds__((WAVE * GineQ<CIN, CHID, COUT, NT, NET, ED, EG>::WP
           add_where<AccPriv, 4>(q, on, tot);
         }
       }
-      GSTAMP(4);
+      STAMP(4);
       // ---- d eps, d x (self term), and dh rows for the edge phase
 #pragma unroll
       for (int mt = 0; mt < MI; ++mt) {
@@ -584,7 +567,7 @@ __global__ __launch_bounds__((WAVE * GineQ<CIN, CHID, COUT, NT, NET, ED, EG>::WP
       WAVE_LDS_SYNC();
     }
 
-    GSTAMP(5);
+    STAMP(5);
     // ---- C. edges again: d message -> sources, lin weight gradients
     for (int32_t c0 = e0; c0 < e1; c0 += NTL * TILE) {
       const int lane = opaque_lane(lane0), i = lane & 15, g = lane >> 4;
@@ -683,7 +666,7 @@ __global__ __launch_bounds__((WAVE * GineQ<CIN, CHID, COUT, NT, NET, ED, EG>::WP
     }
     WAVE_LDS_SYNC();
   }
-  GSTAMP(6);
+  STAMP(6);
   // d eps: sum over the lanes of the wave, into the private block
   for (int off = 32; off > 0; off >>= 1) acc_eps += __shfl_down(acc_eps, off);
   if (lane0 == 0) blk[Q::L_EPS] += acc_eps;
@@ -696,7 +679,7 @@ __global__ __launch_bounds__((WAVE * GineQ<CIN, CHID, COUT, NT, NET, ED, EG>::WP
     for (int ww = 0; ww < GQ_WPB; ++ww) s += blocks[ww * Q::BLK + k];
     out[k] = s;
   }
-  GSTAMP(7);
+  STAMP(7);
 }
 
 // ---------------------------------------------------------------- forward on the same tiles

@@ -11,6 +11,15 @@
 // cgvp_dims.layer_kind; gvp_quad.h LayerKind).  bf16 storage exists for CASTER-DTA's layers only.
 constexpr int POLICY_F32 = 0, POLICY_BF16 = 1, POLICY_GVPDEF = 2, POLICY_LINEAR = 3;
 
+// Small host helpers of the entry points.
+inline int64_t up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+inline int num_convs_of(const cgvp_layout& l) { return l.conv_stride > 0 ? (l.ln_out - l.conv0) / l.conv_stride : 0; }
+// floats of a GINE layer's parameters / gradient block, state_dict order:
+// eps | nn.lins.0.weight | nn.lins.0.bias | nn.lins.1.weight | nn.lins.1.bias | lin.weight | lin.bias
+constexpr int gine_layer_floats(int cin, int chid, int cout, int ke) {
+  return 1 + chid * cin + chid + cout * chid + cout + cin * ke + cin;
+}
+
 // Float offsets of the per-kernel slices inside the fragment image.
 struct QuadOffsets {
   int emb, conv0, node0, layer_stride, head, total;

@@ -52,7 +52,6 @@ inline EncLayout cvt(const cgvp_layout& l) {
   L.ln_out = l.ln_out; L.head = l.head; L.total = l.total;
   return L;
 }
-inline int num_convs_of(const cgvp_layout& l) { return l.conv_stride > 0 ? (l.ln_out - l.conv0) / l.conv_stride : 0; }
 
 // what every fine-grained backward entry point looks up first: the image offsets and the slab row sizes of the layout
 struct BwdLookup : QuadOffsets { quad::BwdBlocks blk; };
@@ -663,10 +662,8 @@ __global__ __launch_bounds__(WAVE * GINE_APB) void gine_conv_kernel(GineArgs a) 
 
 // ------------------------------------------------------------- GINE backward
 // Runs on 16-atom MFMA tiles: gine_quad_kernels.hip.  The layer's gradient block is in state_dict
-// order  eps | nn.lins.0.weight | nn.lins.0.bias | nn.lins.1.weight | nn.lins.1.bias | lin.weight | lin.bias.
-constexpr int gine_layer_floats(int cin, int chid, int cout, int ke) {
-  return 1 + chid * cin + chid + cout * chid + cout + cin * ke + cin;
-}
+// order  eps | nn.lins.0.weight | nn.lins.0.bias | nn.lins.1.weight | nn.lins.1.bias | lin.weight | lin.bias
+// (gine_layer_floats, gvp_internal.h).
 
 }  // namespace
 

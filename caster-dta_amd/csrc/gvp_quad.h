@@ -32,6 +32,7 @@
 #include <hip/hip_runtime.h>
 
 #include "gvp_math.h"
+#include "gvp_rng.h"
 
 namespace gq {
 
@@ -39,6 +40,52 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 
 constexpr int P1 = 0, P2 = 1;
 constexpr int ceil4(int x) { return (x + 3) / 4; }
+constexpr int pad4(int x) { return (x + 3) / 4 * 4; }
+constexpr int WAVE = 64, TILE = 16;
+
+// ---- helpers shared by the tile-kernel units (gvp_quad_kernels, gvp_quad_bwd_kernels, gine_quad_kernels) ------------
+// Workgroup-cooperative copy of an image slice (NFLOATS, multiple of 4) into LDS by NTHR threads:
+// every global load is issued before the first LDS store, so the slice costs one
+// memory latency instead of one per iteration.
+template <int NFLOATS, int NTHR>
+__device__ __forceinline__ void stage_slice(float* lds, const float* __restrict__ src, int tid) {
+  static_assert(NFLOATS % 4 == 0, "image slices are whole float4s");
+  constexpr int NF4 = NFLOATS / 4, IT = (NF4 + NTHR - 1) / NTHR;
+  const f4* s = reinterpret_cast<const f4*>(src);
+  f4* d = reinterpret_cast<f4*>(lds);
+  f4 v[IT];
+#pragma unroll
+  for (int k = 0; k < IT; ++k) { const int idx = tid + k * NTHR; if (idx < NF4) v[k] = s[idx]; }
+#pragma unroll
+  for (int k = 0; k < IT; ++k) { const int idx = tid + k * NTHR; if (idx < NF4) d[idx] = v[k]; }
+}
+
+// Lane id the compiler cannot see through.  Taken at the top of every tile: the ~150 lane-dependent
+// flush addresses (and friends) of a tile are then recomputed per tile with a few VALU ops instead of
+// being hoisted out of the tile loop, spilled to scratch and reloaded one memory round trip at a time.
+__device__ __forceinline__ int opaque_lane(int lane) {
+  asm volatile("" : "+v"(lane));
+  return lane;
+}
+
+// Dropout mask row of a residue: 16 scalar-channel + 4 vector-channel factors (0 or 1/(1-p); a vector channel's xyz
+// share one factor, gvp_layers.py:187-198).
+constexpr int MROW = gvp::NS + gvp::NV;
+// Dropout factors of node n for lane (i, g): scalar channels 4g..4g+3 and vector channel g of mask `which`
+// (0 = dropout[0] on dh, 1 = dropout[1] on the feed-forward output): read from the given mask, or generated --
+// the forward and the backward that recomputes it get the same factors.
+__device__ __forceinline__ void node_dropout(const float* mask, const gvp::RngArgs& rng, int which, int64_t n, int g,
+                                             f4& ms, float& mv) {
+  if (mask) {
+    ms = *reinterpret_cast<const f4*>(mask + n * MROW + 4 * g);
+    mv = mask[n * MROW + gvp::NS + g];
+  } else if (rng.seed) {
+    const unsigned long long seed = rng.seed[0], off = rng.seed[1];
+    float fs[4];
+    gvp::dropout_row20(seed, off, rng.stream + which, n, g, rng.p, fs, mv);
+    ms = f4{fs[0], fs[1], fs[2], fs[3]};
+  }
+}
 
 // ---- activation storage type (cgvp_dims.storage): what the ACTIVATION buffers in HBM hold -- node / edge features,
 // node rows h / dh between stages, the edge-embedding store, the residue embeddings `out`.  fp32 (default) or bf16
@@ -703,90 +750,13 @@ struct GvpQ {
 
   // Backward of `forward` for one tile.  d_so / d_vo: gradients of the outputs;
   // d_bs / d_bv: gradients of the k-slot inputs (same slots as bs / bv).
+  // = backward_tn<1> below, with every argument viewed as a one-element array.
+  template <class T> static __device__ __forceinline__ T (&one(T& x))[1] { return reinterpret_cast<T (&)[1]>(x); }
   template <bool BF = false>
   static __device__ __forceinline__ void backward(const float* imgT, int lane, const Cache& c,
                                                   const f4 (&d_so)[OT], const float (&d_vo)[3][VOR],
                                                   float (&d_bs)[SSTEPS], float (&d_bv)[3][VSTEPS], Grads& gr) {
-    const f4 zero = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int t = 0; t < OT; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) gr.dsp[t][r] = (RELU && c.sp[t][r] <= 0.f) ? 0.f : d_so[t][r];
-    gr.dgate = zero;
-#pragma unroll
-    for (int p = 0; p < 3; ++p) gr.dvp[p] = gr.dvh[p] = zero;
-    if (VO > 0) {
-#pragma unroll
-      for (int r = 0; r < VOR; ++r) {
-        const float sg = c.sg[r];
-        float dsg = 0.f;
-#pragma unroll
-        for (int p = 0; p < 3; ++p) { dsg = fmaf(d_vo[p][r], c.vp[p][r], dsg); gr.dvp[p][r] = d_vo[p][r] * sg; }
-        if (VM == VM_GATE) gr.dgate[r] = dsg * sg * (1.0f - sg);
-        if (VM == VM_NORM) {            // vo = vp sigmoid(n), n = sqrt(max(|vp|^2, eps)): no gradient through n below the clamp
-          const float n2 = c.vp[0][r] * c.vp[0][r] + c.vp[1][r] * c.vp[1][r] + c.vp[2][r] * c.vp[2][r];
-          const float k = n2 > gvp::kNormEps ? dsg * sg * (1.0f - sg) * gvp::f_rsqrt(n2) : 0.f;
-#pragma unroll
-          for (int p = 0; p < 3; ++p) gr.dvp[p][r] = fmaf(k, c.vp[p][r], gr.dvp[p][r]);
-        }
-      }
-      if (VM == VM_GATE) {
-        float bg[1][TWsv::NSTEPS];
-#pragma unroll
-        for (int r = 0; r < TWsv::NSTEPS; ++r) bg[0][r] = gr.dgate[r];
-#pragma unroll
-        for (int t = 0; t < OT; ++t) {
-          f4 acc[1] = {gr.dsp[t]};
-          apply<TWsv, 1, BF>(imgT + FT_WSV * 64, t, bg, acc, lane);
-          gr.dsp[t] = acc[0];
-        }
-      }
-#pragma unroll
-      for (int p = 0; p < 3; ++p) {
-        float b[1][TWv::NSTEPS];
-#pragma unroll
-        for (int r = 0; r < TWv::NSTEPS; ++r) b[0][r] = gr.dvp[p][r];
-        f4 acc[1] = {zero};
-        apply<TWv, 1, BF>(imgT + FT_WV * 64, 0, b, acc, lane);
-        gr.dvh[p] = acc[0];
-      }
-    }
-    float d_vn[HR];
-    {
-      float bd[1][4 * OT];
-#pragma unroll
-      for (int t = 0; t < OT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) bd[0][4 * t + r] = gr.dsp[t][r];
-#pragma unroll
-      for (int mt = 0; mt < TWs::MT; ++mt) {
-        f4 acc[1] = {zero};
-        apply<TWs, 1, BF>(imgT + FT_WS * 64, mt, bd, acc, lane);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int slot = 4 * mt + r;
-          if (slot < SSTEPS) d_bs[slot] = acc[0][r];
-          else if (slot < SSTEPS + HR) d_vn[slot - SSTEPS] = acc[0][r];
-        }
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < HR; ++r) {      // through vn = sqrt(max(|vh|^2, eps)): no gradient below the clamp
-      const float n2 = c.vh[0][r] * c.vh[0][r] + c.vh[1][r] * c.vh[1][r] + c.vh[2][r] * c.vh[2][r];
-      const float k = n2 > gvp::kNormEps ? d_vn[r] * gvp::f_rcp(c.vn[r]) : 0.f;
-#pragma unroll
-      for (int p = 0; p < 3; ++p) gr.dvh[p][r] = fmaf(k, c.vh[p][r], gr.dvh[p][r]);
-    }
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-      float b[1][TWh::NSTEPS];
-#pragma unroll
-      for (int r = 0; r < TWh::NSTEPS; ++r) b[0][r] = gr.dvh[p][r];
-      f4 acc[1] = {zero};
-      apply<TWh, 1, BF>(imgT + FT_WH * 64, 0, b, acc, lane);
-#pragma unroll
-      for (int s2 = 0; s2 < VSTEPS; ++s2) d_bv[p][s2] = acc[0][s2];
-    }
+    backward_tn<1, BF>(imgT, lane, one(c), one(d_so), one(d_vo), one(d_bs), one(d_bv), one(gr));
   }
 
   // Weight gradients of this GVP for one tile, written (first) / added into the
@@ -955,9 +925,9 @@ struct GvpQ {
   }
 
   // ================================================================ lockstep tiles (round 4)
-  // The same backward for TN tiles IN LOCKSTEP: every transposed weight fragment is read from LDS once and feeds TN
-  // independent MFMA chains (as `forward<TN>` does), so a wave that runs alone on its SIMD has independent work to issue
-  // while one tile's chain waits for its accumulator.  Arithmetic per tile identical to `backward`.
+  // The backward for TN tiles IN LOCKSTEP (the ONE body; `backward` is TN = 1): every transposed weight fragment is read
+  // from LDS once and feeds TN independent MFMA chains (as `forward<TN>` does), so a wave that runs alone on its SIMD has
+  // independent work to issue while one tile's chain waits for its accumulator.
   template <int TN, bool BF = false>
   static __device__ __forceinline__ void backward_tn(const float* imgT, int lane, const Cache (&c)[TN],
                                                      const f4 (&d_so)[TN][OT], const float (&d_vo)[TN][3][VOR],
@@ -983,7 +953,7 @@ struct GvpQ {
 #pragma unroll
           for (int p = 0; p < 3; ++p) { dsg = fmaf(d_vo[j][p][r], c[j].vp[p][r], dsg); gr[j].dvp[p][r] = d_vo[j][p][r] * sg; }
           if (VM == VM_GATE) gr[j].dgate[r] = dsg * sg * (1.0f - sg);
-          if (VM == VM_NORM) {
+          if (VM == VM_NORM) {            // vo = vp sigmoid(n), n = sqrt(max(|vp|^2, eps)): no gradient through n below the clamp
             const float n2 = c[j].vp[0][r] * c[j].vp[0][r] + c[j].vp[1][r] * c[j].vp[1][r] + c[j].vp[2][r] * c[j].vp[2][r];
             const float k = n2 > gvp::kNormEps ? dsg * sg * (1.0f - sg) * gvp::f_rsqrt(n2) : 0.f;
 #pragma unroll
@@ -1049,7 +1019,7 @@ struct GvpQ {
 #pragma unroll
     for (int j = 0; j < TN; ++j)
 #pragma unroll
-      for (int r = 0; r < HR; ++r) {
+      for (int r = 0; r < HR; ++r) {      // through vn = sqrt(max(|vh|^2, eps)): no gradient below the clamp
         const float n2 = c[j].vh[0][r] * c[j].vh[0][r] + c[j].vh[1][r] * c[j].vh[1][r] + c[j].vh[2][r] * c[j].vh[2][r];
         const float k = n2 > gvp::kNormEps ? d_vn[j][r] * gvp::f_rcp(c[j].vn[r]) : 0.f;
 #pragma unroll

@@ -26,63 +26,25 @@
 #include "gvp_internal.h"
 #include "gvp_quad.h"
 
-using namespace gq;
-
-#ifdef CGVP_STAMPS
+#ifdef CGVP_STAMPS                     // diagnostic build only
 __device__ unsigned long long* g_stamp_buf_bwd = nullptr;
 extern "C" int cgvp_debug_set_stamp_buffer_bwd(unsigned long long* buf) {
   return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_buf_bwd), &buf, sizeof(buf));
 }
 #endif
+#define CGVP_STAMP_BUF g_stamp_buf_bwd
+#include "gvp_stamp.h"
+
+using namespace gq;
 
 namespace {
 
-constexpr int WAVE = 64;
-constexpr int TILE = 16;
-
-#ifdef CGVP_STAMPS     // diagnostic build only, see gvp_quad_kernels.hip
-#define STAMP(slot)                                                                          \
-  do {                                                                                       \
-    __builtin_amdgcn_sched_barrier(0);                                                       \
-    unsigned long long t_;                                                                   \
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory"); \
-    __builtin_amdgcn_sched_barrier(0);                                                       \
-    if (g_stamp_buf_bwd && (threadIdx.x & 63) == 0)                                          \
-      g_stamp_buf_bwd[((size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 16 + (slot)] = t_;    \
-  } while (0)
-// wall-clock start / end of every wave of a kernel (s_memrealtime: 100 MHz, one counter for the whole device), kept per
-// kernel kind behind the cycle stamps: buffer[4096 * 16 + (kind * 4096 + wave) * 2 + {0: start, 1: end}]
-struct WallStamp {
-  int kind;
-  __device__ __forceinline__ explicit WallStamp(int k) : kind(k) { put(0); }
-  __device__ __forceinline__ ~WallStamp() { put(1); }
-  __device__ __forceinline__ void put(int which) const {
-    unsigned long long t_;
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");
-    const size_t wave = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (g_stamp_buf_bwd && (threadIdx.x & 63) == 0 && wave < 4096)
-      g_stamp_buf_bwd[4096 * 16 + ((size_t)kind * 4096 + wave) * 2 + which] = t_;
-  }
-};
-#define WALL_STAMP(kind) WallStamp wall_stamp_(kind)
-#else
-#define STAMP(slot) do {} while (0)
-#define WALL_STAMP(kind) do {} while (0)
-#endif
 // Every backward kernel runs ONE workgroup of 8 waves per CU (2 per SIMD) that owns the CU's
 // LDS: [trash word per thread | image slices | one private weight-gradient block per wave (AccPriv)].  Waves take
 // tiles round-robin across workgroups, so a small batch still spreads over all CUs; at the
 // end the workgroup sums its waves' blocks and writes ONE slab row.
 constexpr int BW_WPB = 8, BW_TPB = WAVE * BW_WPB, BW_MAX_GRID = kBwdMaxGrid;
 static_assert(BW_MAX_GRID <= 256, "at most one workgroup per CU");
-
-// Lane id the compiler cannot see through.  Taken at the top of every tile: the ~150 lane-dependent
-// flush addresses (and friends) of a tile are then recomputed per tile with a few VALU ops instead of
-// being hoisted out of the tile loop, spilled to scratch and reloaded one memory round trip at a time.
-__device__ __forceinline__ int opaque_lane(int lane) {
-  asm volatile("" : "+v"(lane));
-  return lane;
-}
 
 template <int BLK>
 __device__ __forceinline__ void zero_block(float* gblk, int lane) {
@@ -91,8 +53,9 @@ __device__ __forceinline__ void zero_block(float* gblk, int lane) {
 }
 // slab row of this workgroup = sum of its waves' private blocks (stride PW floats apart)
 template <int BLK, int PW, int WPB_ = 8>
-__device__ __forceinline__ void write_slab_row(float* slab, const float* blocks, int row = blockIdx.x) {
+__device__ __forceinline__ void write_slab_row(float* slab, const float* blocks) {
   __syncthreads();
+  const int row = blockIdx.x;
   float* out = slab + (size_t)row * BLK;
   for (int k = threadIdx.x; k < BLK; k += WAVE * WPB_) {
     float t = 0.f;
@@ -102,25 +65,11 @@ __device__ __forceinline__ void write_slab_row(float* slab, const float* blocks,
   }
 }
 
-template <int NFLOATS, int NTHR>
-__device__ __forceinline__ void stage_slice(float* lds, const float* __restrict__ src, int tid) {
-  static_assert(NFLOATS % 4 == 0, "image slices are whole float4s");
-  constexpr int NF4 = NFLOATS / 4, IT = (NF4 + NTHR - 1) / NTHR;
-  const f4* s = reinterpret_cast<const f4*>(src);
-  f4* d = reinterpret_cast<f4*>(lds);
-  f4 v[IT];
-#pragma unroll
-  for (int k = 0; k < IT; ++k) { const int idx = tid + k * NTHR; if (idx < NF4) v[k] = s[idx]; }
-#pragma unroll
-  for (int k = 0; k < IT; ++k) { const int idx = tid + k * NTHR; if (idx < NF4) d[idx] = v[k]; }
-}
-
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
 // ONE = every wave of the launch has at most one tile (the host checks tiles <= grid x waves): a wave's private block is
 // still all zeros when its only tile adds to it, so the adds are plain stores -- no LDS read in front of each write
 // (the node / head / embed stages at 64 x 300 residues are exactly this case)
 template <bool ONE> using AccFor = typename std::conditional<ONE, AccStoreOnce, AccPriv>::type;
-constexpr int pad4(int x) { return (x + 3) / 4 * 4; }
 
 // LayerNorm parameter gradients of a tile -> [gamma | beta] block in LDS.
 template <class Acc, int S>
@@ -152,20 +101,6 @@ constexpr int NB_LN0 = 0, NB_LN1 = 2 * NS, NB_FF0 = 4 * NS, NB_FF1 = NB_FF0 + LF
 constexpr int HB_LN = 0, HB_GVP = 2 * NS, HEAD_BLK = HB_GVP + LHead::size(0);
 constexpr int NODE_GB = pad4(NODE_BLK), HEAD_GB = pad4(HEAD_BLK);
 
-constexpr int MROW = NS + NV;          // dropout mask row: 16 scalar + 4 vector-channel factors
-// factors of node n for lane (i, g): given mask row or regenerated (same function as the forward, gvp_quad_kernels.hip)
-__device__ __forceinline__ void node_dropout(const float* mask, const gvp::RngArgs& rng, int which, int64_t n, int g,
-                                             f4& ms, float& mv) {
-  if (mask) {
-    ms = *reinterpret_cast<const f4*>(mask + n * MROW + 4 * g);
-    mv = mask[n * MROW + NS + g];
-  } else if (rng.seed) {
-    const unsigned long long seed = rng.seed[0], off = rng.seed[1];
-    float fs[4];
-    gvp::dropout_row20(seed, off, rng.stream + which, n, g, rng.p, fs, mv);
-    ms = f4{fs[0], fs[1], fs[2], fs[3]};
-  }
-}
 struct NodeBArgs {
   const float* img_node; const float* imgT_node;
   const float* h; const float* dh; const float* mask0; const float* mask1; gvp::RngArgs rng;
@@ -1091,13 +1026,13 @@ template <int NTE>
 constexpr int edge_bwd_lds_floats() { return BW_TPB + Image<0, NTE>::CV_M0 + Image<0, NTE>::TC_M0 + BW_WPB * (EdgeBlk<NTE>::SIZE + TSCR_FLOATS); }
 
 template <int NTE, typename ST, bool DX>
-__device__ __forceinline__ void edge_bwd_body(const EdgeBArgs& a, float* lds, int bid, int nblk) {
+__device__ __forceinline__ void edge_bwd_body(const EdgeBArgs& a, float* lds) {
   typedef Image<0, NTE> IM;
   typedef EdgeBlk<NTE> B;
   constexpr int PW = B::SIZE + TSCR_FLOATS;
   float* img = lds + BW_TPB;                      // [QEdge | edge LN]  (= the first CV_M0 floats of the conv slice)
   float* imgT = img + IM::CV_M0;                  // QEdge transposed  (= the first TC_M0 floats of the convT slice)
-  const int lane0 = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int lane0 = threadIdx.x & 63, w = threadIdx.x >> 6, bid = blockIdx.x, nblk = gridDim.x;
   float* blocks = imgT + IM::TC_M0;
   float* gblk = blocks + w * PW;
   float* tscr = gblk + B::SIZE;
@@ -1174,13 +1109,13 @@ __device__ __forceinline__ void edge_bwd_body(const EdgeBArgs& a, float* lds, in
     QEdge<NTE>::template wacc_accumulate<1, Io<ST>::BF>(wacc, lane, et, bse, bve, ce, gr, tscr);
   }
   QEdge<NTE>::template wacc_flush<AccStoreOnce>(wacc, gblk + B::GVP, lane0);
-  write_slab_row<B::SIZE, PW>(a.slab, blocks, bid);
+  write_slab_row<B::SIZE, PW>(a.slab, blocks);
 }
 template <int NTE, typename ST, bool DX = false>
 __global__ __launch_bounds__(BW_TPB) __attribute__((amdgpu_waves_per_eu(4, 4))) void edge_bwd_kernel(EdgeBArgs a) {
   WALL_STAMP(3);
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  edge_bwd_body<NTE, ST, DX>(a, lds, blockIdx.x, gridDim.x);
+  edge_bwd_body<NTE, ST, DX>(a, lds);
 }
 
 // ===================================================================== node embed
@@ -1198,7 +1133,7 @@ template <int NTN>
 constexpr int embed_bwd_lds_floats() { return BW_TPB + Image<NTN, 0>::EMB_SIZE + Image<NTN, 0>::TE_SIZE + BW_WPB * (EmbBlk<NTN>::SIZE + TSCR_FLOATS); }
 
 template <int NTN, typename ST, bool ONE = false>
-__device__ __forceinline__ void embed_bwd_body(const EmbBArgs& a, float* lds, int bid, int nblk) {
+__device__ __forceinline__ void embed_bwd_body(const EmbBArgs& a, float* lds) {
   typedef Image<NTN, 0> IM;
   typedef AccFor<ONE> Acc;
   typedef QNode<NTN> Q;
@@ -1206,7 +1141,7 @@ __device__ __forceinline__ void embed_bwd_body(const EmbBArgs& a, float* lds, in
   float* img = lds + BW_TPB;
   float* imgT = img + IM::EMB_SIZE;
   float* blocks = imgT + IM::TE_SIZE;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, bid = blockIdx.x, nblk = gridDim.x;
   float* gblk = blocks + w * B::SIZE;                               // this wave's private gradient block
   float* tscr = blocks + BW_WPB * B::SIZE + w * TSCR_FLOATS;
   stage_slice<IM::EMB_SIZE, BW_TPB>(img, a.img, threadIdx.x);
@@ -1269,13 +1204,13 @@ __device__ __forceinline__ void embed_bwd_body(const EmbBArgs& a, float* lds, in
       }
     }
   }
-  write_slab_row<B::SIZE, B::SIZE>(a.slab, blocks, bid);
+  write_slab_row<B::SIZE, B::SIZE>(a.slab, blocks);
 }
 template <int NTN, typename ST, bool ONE = false>
 __global__ __launch_bounds__(BW_TPB, 2) void embed_bwd_kernel(EmbBArgs a) {
   WALL_STAMP(4);
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  embed_bwd_body<NTN, ST, ONE>(a, lds, blockIdx.x, gridDim.x);
+  embed_bwd_body<NTN, ST, ONE>(a, lds);
 }
 
 // dst[j] += sum_r slab[r][col0 + j], j < len.  A block owns 64 columns; its 16

@@ -15,63 +15,20 @@
 #include "gvp_internal.h"
 #include "gvp_quad.h"
 
+#ifdef CGVP_STAMPS                     // diagnostic build only
+namespace { __device__ unsigned long long* g_stamp_buf = nullptr; }
+#endif
+#define CGVP_STAMP_BUF g_stamp_buf
+#define CGVP_STAMP_WPB WPB
+#include "gvp_stamp.h"
+
 using namespace gq;
 
 namespace {
 
-// Diagnostic build only (-DCGVP_STAMPS): per-wave s_memtime stamps into a debug
-// buffer that nothing else reads; the production library contains none of it.
-#ifdef CGVP_STAMPS
-__device__ unsigned long long* g_stamp_buf = nullptr;
-#define STAMP(slot)                                                                          \
-  do {                                                                                       \
-    __builtin_amdgcn_sched_barrier(0);                                                       \
-    unsigned long long t_;                                                                   \
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory"); \
-    __builtin_amdgcn_sched_barrier(0);                                                       \
-    if (g_stamp_buf && (threadIdx.x & 63) == 0)                                              \
-      g_stamp_buf[((size_t)blockIdx.x * WPB + (threadIdx.x >> 6)) * 16 + (slot)] = t_;        \
-  } while (0)
-// wall-clock stamp (s_memrealtime: 100 MHz, one counter for the whole device -- s_memtime counters are per XCD)
-#define STAMP_REAL(slot)                                                                     \
-  do {                                                                                       \
-    unsigned long long t_;                                                                   \
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");           \
-    if (g_stamp_buf && (threadIdx.x & 63) == 0)                                              \
-      g_stamp_buf[((size_t)blockIdx.x * WPB + (threadIdx.x >> 6)) * 16 + (slot)] = t_;        \
-  } while (0)
-#else
-#define STAMP(slot) do {} while (0)
-#define STAMP_REAL(slot) do {} while (0)
-#endif
-
-constexpr int WAVE = 64;
 constexpr int WPB = 4;                 // waves per workgroup
 constexpr int TPB = WAVE * WPB;
 constexpr int gq_fwd_tpb = TPB;
-constexpr int TILE = 16;
-
-// Workgroup-cooperative copy of an image slice (NFLOATS, multiple of 4) into LDS:
-// every global load is issued before the first LDS store, so the slice costs one
-// memory latency instead of one per iteration.
-template <int NFLOATS>
-__device__ __forceinline__ void stage_slice(float* lds, const float* __restrict__ src, int tid) {
-  static_assert(NFLOATS % 4 == 0, "image slices are whole float4s");
-  constexpr int NF4 = NFLOATS / 4, IT = (NF4 + TPB - 1) / TPB;
-  const f4* s = reinterpret_cast<const f4*>(src);
-  f4* d = reinterpret_cast<f4*>(lds);
-  f4 v[IT];
-#pragma unroll
-  for (int k = 0; k < IT; ++k) {
-    const int idx = tid + k * TPB;
-    if (idx < NF4) v[k] = s[idx];
-  }
-#pragma unroll
-  for (int k = 0; k < IT; ++k) {
-    const int idx = tid + k * TPB;
-    if (idx < NF4) d[idx] = v[k];
-  }
-}
 
 // Up to three slices (from three places of the image) into consecutive LDS: ALL global loads are issued before the
 // first LDS store, so the copies cost one memory latency together instead of one each (the fused conv + node update
@@ -207,7 +164,7 @@ template <int NTN, typename ST>
 __global__ __launch_bounds__(TPB) void embed_quad_kernel(EmbedQArgs a) {
   typedef Image<NTN, 0> IM;
   __shared__ __attribute__((aligned(16))) float lds[IM::EMB_SIZE];
-  stage_slice<IM::EMB_SIZE>(lds, a.img, threadIdx.x);
+  stage_slice<IM::EMB_SIZE, TPB>(lds, a.img, threadIdx.x);
   rng_handoff(a);
   __syncthreads();
   embed_tile<NTN, ST>(a, lds, blockIdx.x);
@@ -251,31 +208,14 @@ __global__ __launch_bounds__(TPB) void pass_begin_kernel(PassBeginArgs a) {
 }
 
 // ------------------------------------------------------------------ node update
-// mask0 / mask1: optional dropout masks [N][20] = 16 scalar-channel + 4 vector-channel
-// factors (0 or 1/(1-p); a vector channel's xyz share one factor, gvp_layers.py:187-198),
-// applied to dh before the first residual and to the feed-forward output before the second.
+// mask0 / mask1: optional dropout masks [N][MROW] (gvp_quad.h, node_dropout), applied to dh before the first
+// residual and to the feed-forward output before the second.
 struct NodeQArgs {
   const float* img_node; const float* img_head;
   const float* h; const float* dh; int64_t N; float* h_out; float* out;
   const float* mask0; const float* mask1;
   gvp::RngArgs rng;            // in-kernel dropout (used where the mask pointers are NULL); stream = 2 * layer
 };
-constexpr int MROW = NS + NV;
-
-// Dropout factors of node n for lane (i, g): scalar channels 4g..4g+3 and vector channel g of mask `which`
-// (0 = dropout[0] on dh, 1 = dropout[1] on the feed-forward output): read from the given mask, or generated.
-__device__ __forceinline__ void node_dropout(const float* mask, const gvp::RngArgs& rng, int which, int64_t n, int g,
-                                             f4& ms, float& mv) {
-  if (mask) {
-    ms = *reinterpret_cast<const f4*>(mask + n * MROW + 4 * g);
-    mv = mask[n * MROW + NS + g];
-  } else if (rng.seed) {
-    const unsigned long long seed = rng.seed[0], off = rng.seed[1];
-    float fs[4];
-    gvp::dropout_row20(seed, off, rng.stream + which, n, g, rng.p, fs, mv);
-    ms = f4{fs[0], fs[1], fs[2], fs[3]};
-  }
-}
 
 // Rest of GVPConvLayer.forward for one tile of 16 residues, from s/v = h + mask0 * dh (lane (i, g)
 // holds scalars 4g..4g+3 and vector channel g): LN0, feed-forward GVPs, residual, LN1 -> h_out
@@ -392,7 +332,7 @@ struct ConvQArgs {
   // and the backward kernels read it (e_in) instead of re-deriving it from the raw features
   const float* e_in; float* e_out; int64_t E;      // e_out holds E + 1 rows: row E is a spare that masked-off lanes write
 };
-constexpr int EROW = 36;
+constexpr int EROW = quad::kEdgeRow;
 // EMODE of the conv kernel: 0 = derive the edge embedding from the raw features (and keep it in registers),
 // 1 = derive it and also store it to e_out, 2 = read it from e_in (raw features untouched)
 

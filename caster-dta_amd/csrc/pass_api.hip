@@ -44,18 +44,13 @@ struct Timed {                 // brackets one launch with events when timing is
   }
 };
 
-constexpr int ROW = 28;                 // merged node row [s(16) | v(4x3)]
-constexpr int EROW = CGVP_EDGE_ROW;
-constexpr int MROW = 20;                // dropout mask row: 16 scalar + 4 vector-channel factors
-
-inline int64_t up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+using gvp::ROW;                        // merged node row [s(16) | v(4x3)]
 // A/B switch (environment, read once): CGVP_GINE_RECOMPUTE=1 makes the drug backward recompute its aggregates as it did
 // until round 3 instead of reading what the forward saved (the forward then saves nothing).
 inline bool gine_recompute() {
   static const bool v = [] { const char* e = getenv("CGVP_GINE_RECOMPUTE"); return e && e[0] == '1'; }();
   return v;
 }
-inline int num_convs_of(const cgvp_layout& l) { return l.conv_stride > 0 ? (l.ln_out - l.conv0) / l.conv_stride : 0; }
 inline int esize(const cgvp_dims* d) { return d->storage == CGVP_BF16 ? 2 : 4; }
 template <typename T>
 inline T* at(void* base, int64_t off) { return reinterpret_cast<T*>(reinterpret_cast<char*>(base) + off); }
@@ -67,8 +62,17 @@ struct Bump {          // 256-B aligned sub-buffer offsets
   int64_t take(int64_t bytes) { const int64_t o = off; off = up(off + (bytes > 0 ? bytes : 0), 256); return o; }
 };
 
-inline bool has_tables(const cgvp_lba_batch* b) { return b->rowptr != nullptr; }
-inline bool has_tables(const cgvp_gine_batch* b) { return b->rowptr != nullptr; }
+// The dst-sorted CSR tables of a pass: the collated ones the batch brings, or the ones the forward built in its workspace.
+// Batch / Ws: cgvp_lba_batch + cgvp_lba_fwd_ws or cgvp_gine_batch + cgvp_gine_fwd_ws (the fields have the same names).
+template <class Batch>
+inline bool has_tables(const Batch* b) { return b->rowptr != nullptr; }
+struct CsrTables { const int32_t *rowptr, *eperm, *esrc, *edst; };
+template <class Batch, class Ws>
+inline CsrTables tables_of(const Batch* b, const void* workspace, const Ws& ws) {
+  if (has_tables(b)) return CsrTables{b->rowptr, b->eperm, b->esrc, b->edst};
+  return CsrTables{at<int32_t>(workspace, ws.rowptr), at<int32_t>(workspace, ws.eperm), at<int32_t>(workspace, ws.esrc),
+                   at<int32_t>(workspace, ws.edst)};
+}
 
 // ------------------------------------------------------------------ protein backward workspace
 // deterministic mode: behind the default layout, the source-order index and the stored rows
@@ -94,7 +98,7 @@ int lba_bwd_layout(const cgvp_dims* dims, const cgvp_layout* layout, int64_t N, 
   Bump b;
   w->slab_floats = wsz;
   w->slabs = b.take((int64_t)(2 * nc + 2) * wsz * 4);
-  w->g_e_stride = up((E + 1) * EROW * 4, 256) / 4;
+  w->g_e_stride = up((E + 1) * CGVP_EDGE_ROW * 4, 256) / 4;
   w->g_e = b.take((int64_t)nc * w->g_e_stride * 4);
   w->row_floats = up(N * ROW * 4, 256) / 4;
   w->rows = b.take(8 * w->row_floats * 4);
@@ -106,9 +110,6 @@ int lba_bwd_layout(const cgvp_dims* dims, const cgvp_layout* layout, int64_t N, 
 }
 
 // ------------------------------------------------------------------ GINE helpers
-inline int gine_layer_floats(int cin, int chid, int cout, int ke) {
-  return 1 + chid * cin + chid + cout * chid + cout + cin * ke + cin;
-}
 int check_gine_cfg(const cgvp_gine_cfg* c) {
   if (!c || c->num_layers < 1 || c->num_layers > CGVP_GINE_MAX_LAYERS) return CGVP_ERR_BAD_ARG;
   if (c->num_ntypes < 0 || c->num_etypes < 0 || c->edge_dim < 0) return CGVP_ERR_BAD_ARG;
@@ -207,7 +208,7 @@ int cgvp_lba_fwd_workspace(const cgvp_dims* dims, const cgvp_layout* layout, int
   out->state = b.take(out->state_rows * out->node_stride * ROW * esize(dims));
   // the CSR build's scratch (edge ids in arrival order, E ints) lives in the edge-embedding store: it is consumed by the
   // ranking launch before conv layer 0 writes the store
-  out->e_emb = b.take((E + 1) * EROW * esize(dims) > E * 4 ? (E + 1) * EROW * esize(dims) : E * 4);
+  out->e_emb = b.take((E + 1) * CGVP_EDGE_ROW * esize(dims) > E * 4 ? (E + 1) * CGVP_EDGE_ROW * esize(dims) : E * 4);
   out->ids_scratch = out->e_emb;
   out->rowptr = b.take((N + 1) * 4);
   out->eperm = b.take((E > 0 ? E : 1) * 4);
@@ -252,10 +253,7 @@ int cgvp_lba_forward_pass(const cgvp_dims* dims, const cgvp_layout* layout, cons
   const int64_t srow = ws.node_stride * ROW * es;        // bytes per state row
   auto row = [&](int64_t r) { return reinterpret_cast<float*>(state + r * srow); };
   float* e_emb = at<float>(workspace, ws.e_emb);
-  int32_t* rowptr = tables ? const_cast<int32_t*>(batch->rowptr) : at<int32_t>(workspace, ws.rowptr);
-  int32_t* eperm = tables ? const_cast<int32_t*>(batch->eperm) : at<int32_t>(workspace, ws.eperm);
-  int32_t* esrc = tables ? const_cast<int32_t*>(batch->esrc) : at<int32_t>(workspace, ws.esrc);
-  int32_t* edst = tables ? const_cast<int32_t*>(batch->edst) : at<int32_t>(workspace, ws.edst);
+  const auto [rowptr, eperm, esrc, edst] = tables_of(batch, workspace, ws);
   const bool count_here = !tables && E > 0;
   // (1) node embedding + fragment image + per-target edge counts, one launch
   if (int rc = cgvp_lba_pass_begin(dims, layout, params, image, batch->x_s, batch->x_v, batch->ntypes, N, row(0),
@@ -265,8 +263,9 @@ int cgvp_lba_forward_pass(const cgvp_dims* dims, const cgvp_layout* layout, cons
   // (2) CSR tables (three launches after the fused count; none when the batch brings collated tables)
   if (!tables) {
     if (!csr_counters) return CGVP_ERR_BAD_ARG;
-    if (int rc = cgvp_csr_from_coo(batch->edge_index, N, E, rowptr, eperm, esrc, edst, csr_counters, count_here ? 2 : 1,
-                                   at<int32_t>(workspace, ws.ids_scratch), stream))
+    if (int rc = cgvp_csr_from_coo(batch->edge_index, N, E, at<int32_t>(workspace, ws.rowptr), at<int32_t>(workspace, ws.eperm),
+                                   at<int32_t>(workspace, ws.esrc), at<int32_t>(workspace, ws.edst), csr_counters,
+                                   count_here ? 2 : 1, at<int32_t>(workspace, ws.ids_scratch), stream))
       return rc;
   }
   if (N == 0) return 0;
@@ -274,7 +273,7 @@ int cgvp_lba_forward_pass(const cgvp_dims* dims, const cgvp_layout* layout, cons
   int32_t fuse_i = 0;
   (void)cgvp_lba_forward_plan(N, E, nc, tables ? 1 : 0, flags, &fuse_i);
   const bool fuse = fuse_i != 0;
-  const int64_t mstride = N * MROW;
+  const int64_t mstride = N * (gvp::NS + gvp::NV);      // dropout mask rows: 16 scalar + 4 vector-channel factors
   for (int l = 0; l < nc; ++l) {
     const bool last = l == nc - 1;
     cgvp_rng rng{draw ? seed : nullptr, dropout_p, 2 * l};
@@ -306,21 +305,19 @@ int cgvp_lba_forward_pass(const cgvp_dims* dims, const cgvp_layout* layout, cons
   return launch_status();
 }
 
-int64_t cgvp_lba_bwd_workspace_bytes_ex(const cgvp_dims* dims, const cgvp_layout* layout, int64_t N, int64_t E,
-                                        int32_t flags) {
+static int64_t lba_bwd_bytes(const cgvp_dims* dims, const cgvp_layout* layout, int64_t N, int64_t E, bool det) {
   if (!dims || !layout || N < 0 || E < 0) return CGVP_ERR_BAD_ARG;
   if (dims->layer_kind != CGVP_LAYER_GATED) return CGVP_ERR_UNSUPPORTED_DIMS;
   LbaBwdWs w;
-  if (int rc = lba_bwd_layout(dims, layout, N, E, &w, det_mode(flags))) return rc;
+  if (int rc = lba_bwd_layout(dims, layout, N, E, &w, det)) return rc;
   return w.total;
 }
-
+int64_t cgvp_lba_bwd_workspace_bytes_ex(const cgvp_dims* dims, const cgvp_layout* layout, int64_t N, int64_t E,
+                                        int32_t flags) {
+  return lba_bwd_bytes(dims, layout, N, E, det_mode(flags));
+}
 int64_t cgvp_lba_bwd_workspace_bytes(const cgvp_dims* dims, const cgvp_layout* layout, int64_t N, int64_t E) {
-  if (!dims || !layout || N < 0 || E < 0) return CGVP_ERR_BAD_ARG;
-  if (dims->layer_kind != CGVP_LAYER_GATED) return CGVP_ERR_UNSUPPORTED_DIMS;
-  LbaBwdWs w;
-  if (int rc = lba_bwd_layout(dims, layout, N, E, &w)) return rc;
-  return w.total;
+  return lba_bwd_bytes(dims, layout, N, E, false);
 }
 
 int cgvp_lba_backward_pass(const cgvp_dims* dims, const cgvp_layout* layout, const cgvp_lba_batch* batch,
@@ -362,11 +359,7 @@ int cgvp_lba_backward_pass_ex(const cgvp_dims* dims, const cgvp_layout* layout, 
   const int64_t srow = ws.node_stride * ROW * es;
   auto row = [&](int64_t r) { return reinterpret_cast<const float*>(state + r * srow); };
   const float* e_emb = at<float>(fwd_workspace, ws.e_emb);
-  const bool tables = has_tables(batch);
-  const int32_t* rowptr = tables ? batch->rowptr : at<int32_t>(fwd_workspace, ws.rowptr);
-  const int32_t* eperm = tables ? batch->eperm : at<int32_t>(fwd_workspace, ws.eperm);
-  const int32_t* esrc = tables ? batch->esrc : at<int32_t>(fwd_workspace, ws.esrc);
-  const int32_t* edst = tables ? batch->edst : at<int32_t>(fwd_workspace, ws.edst);
+  const auto [rowptr, eperm, esrc, edst] = tables_of(batch, fwd_workspace, ws);
   float* slabs = at<float>(bwd_workspace, bw.slabs);
   float* g_e = at<float>(bwd_workspace, bw.g_e);
   float* rows = at<float>(bwd_workspace, bw.rows);
@@ -378,7 +371,7 @@ int cgvp_lba_backward_pass_ex(const cgvp_dims* dims, const cgvp_layout* layout, 
   int32_t cnt = 0;
   auto region = [&]() { return slabs + (int64_t)(stage++) * bw.slab_floats; };
   if (2 * nc + 2 + 1 > CGVP_MAX_SEGS) return CGVP_ERR_UNSUPPORTED_DIMS;
-  const int64_t mstride = N * MROW;
+  const int64_t mstride = N * (gvp::NS + gvp::NV);      // dropout mask rows: 16 scalar + 4 vector-channel factors
   quad::DetBufs db{};
   if (det) {             // the source-order index of the batch's CSR, once for every layer
     const DetWs& d = bw.det_ws;
@@ -480,10 +473,7 @@ int cgvp_gine_forward_pass(const cgvp_gine_cfg* cfg, const cgvp_gine_w* w, const
   if (N > 0 && !out) return CGVP_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
   uint64_t* seed = at<uint64_t>(workspace, ws.seed);
-  const int32_t* rowptr = tables ? batch->rowptr : at<int32_t>(workspace, ws.rowptr);
-  const int32_t* eperm = tables ? batch->eperm : at<int32_t>(workspace, ws.eperm);
-  const int32_t* esrc = tables ? batch->esrc : at<int32_t>(workspace, ws.esrc);
-  const int32_t* edst = tables ? batch->edst : at<int32_t>(workspace, ws.edst);
+  const auto [rowptr, eperm, esrc, edst] = tables_of(batch, workspace, ws);
   if (!tables) {
     // the count launch also advances the dropout generator (no launch of its own)
     if (int rc = quad::csr_build(batch->edge_index, N, E, at<int32_t>(workspace, ws.rowptr), at<int32_t>(workspace, ws.eperm),
@@ -530,20 +520,18 @@ int cgvp_gine_forward_pass(const cgvp_gine_cfg* cfg, const cgvp_gine_w* w, const
   return launch_status();
 }
 
-int64_t cgvp_gine_bwd_workspace_bytes(const cgvp_gine_cfg* cfg, int64_t N, int64_t E) {
+static int64_t gine_bwd_bytes(const cgvp_gine_cfg* cfg, int64_t N, int64_t E, bool det) {
   if (int rc = check_gine_cfg(cfg)) return rc;
   if (N < 0 || E < 0) return CGVP_ERR_BAD_ARG;
   GineBwdWs w;
-  gine_bwd_layout(cfg, N, &w);
+  gine_bwd_layout(cfg, N, &w, E, det);
   return w.total;
 }
-
+int64_t cgvp_gine_bwd_workspace_bytes(const cgvp_gine_cfg* cfg, int64_t N, int64_t E) {
+  return gine_bwd_bytes(cfg, N, E, false);
+}
 int64_t cgvp_gine_bwd_workspace_bytes_ex(const cgvp_gine_cfg* cfg, int64_t N, int64_t E, int32_t flags) {
-  if (int rc = check_gine_cfg(cfg)) return rc;
-  if (N < 0 || E < 0) return CGVP_ERR_BAD_ARG;
-  GineBwdWs w;
-  gine_bwd_layout(cfg, N, &w, E, det_mode(flags));
-  return w.total;
+  return gine_bwd_bytes(cfg, N, E, det_mode(flags));
 }
 
 int cgvp_gine_backward_pass(const cgvp_gine_cfg* cfg, const cgvp_gine_w* w, const cgvp_gine_batch* batch, float dropout_p,
@@ -588,11 +576,7 @@ int cgvp_gine_backward_pass_eattr(const cgvp_gine_cfg* cfg, const cgvp_gine_w* w
   const bool drop = dropout_p > 0.f && L > 1;
   const bool draw = drop && !masks;
   const uint64_t* seed = at<uint64_t>(fwd_workspace, ws.seed);
-  const bool tables = has_tables(batch);
-  const int32_t* rowptr = tables ? batch->rowptr : at<int32_t>(fwd_workspace, ws.rowptr);
-  const int32_t* eperm = tables ? batch->eperm : at<int32_t>(fwd_workspace, ws.eperm);
-  const int32_t* esrc = tables ? batch->esrc : at<int32_t>(fwd_workspace, ws.esrc);
-  const int32_t* edst = tables ? batch->edst : at<int32_t>(fwd_workspace, ws.edst);
+  const auto [rowptr, eperm, esrc, edst] = tables_of(batch, fwd_workspace, ws);
   float* slabs = at<float>(bwd_workspace, bw.slabs);
   float* gx = at<float>(bwd_workspace, bw.gx);
   const DetWs& dw = bw.det_ws;
