@@ -91,11 +91,6 @@ int conv_bwd(int nt_edge, const float* img, const float* imgT, const float* h, c
 // conv_bwd with g_edge / slot: d h[src] rows -> g_edge [E][28] at their sorted positions, boundary rows -> slot
 // [conv_bwd_max_waves()][28]; g_src is not touched (src_sum fills it).  The waves of the launch are *grid x 8.
 int conv_bwd_max_waves();
-// source-order index of a dst-sorted CSR (gvp_kernels.hip): sptr [N+1], spos [E]: the sorted positions p < rowptr[N] of
-// every source in increasing p.  work: src_index_work_ints(N, E) ints, 16-B aligned, any content.  Five launches.
-int64_t src_index_work_ints(int64_t N, int64_t E);
-int src_index(const int32_t* rowptr, const int32_t* esrc, int64_t N, int64_t E, int32_t* sptr, int32_t* spos,
-              int32_t* work, hipStream_t st);
 // out [N][width] = self (optional) + rows[p] over the source's positions (+ slot rows of conv_bwd's boundary targets)
 int src_sum(int width, const float* rows, const float* self, const int32_t* sptr, const int32_t* spos,
             const int32_t* rowptr, const float* slot, int64_t waves, int64_t N, float* out, hipStream_t st);
@@ -137,9 +132,16 @@ int reduce_segments(const cgvp_segment* segs, int nsegs, float* grad_params, hip
 // floats of one slab row (= one workgroup's weight-gradient block) of each backward stage
 struct BwdBlocks { int emb, conv_edge, conv_total, node, head; };
 int bwd_block_sizes(int nt_node, int nt_edge, BwdBlocks* b);
-// gvp_kernels.hip
-void zero_words(void* p, size_t words, hipStream_t s);     // the library's own zero fill (never hipMemsetAsync: see gvp_kernels.hip)
+// ---- graph_index_kernels.hip: zero fill, dst-sorted CSR build, source-order index
+void zero_words(void* p, size_t words, hipStream_t s);     // the library's own zero fill (never hipMemsetAsync: see that file)
 int csr_build(const int64_t* edge_index, int64_t N, int64_t E, int32_t* rowptr, int32_t* eperm, int32_t* esrc,
               int32_t* edst, int32_t* work, int work_is_zero, int32_t* ids_scratch, unsigned long long* rng_state,
               unsigned long long* rng_out, hipStream_t stream);
+// source-order index of a dst-sorted CSR: sptr [N+1], spos [E]: the sorted positions p < rowptr[N] of every source in
+// increasing p.  work: src_index_work_ints(N, E) ints, 16-B aligned, any content.  Five launches.
+int64_t src_index_work_ints(int64_t N, int64_t E);
+int src_index(const int32_t* rowptr, const int32_t* esrc, int64_t N, int64_t E, int32_t* sptr, int32_t* spos,
+              int32_t* work, hipStream_t st);
+// ---- gvp_kernels.hip: cgvp_rng_next without its checks (csr_build's, when it has no count launch to advance the generator in)
+int rng_next(unsigned long long* state, unsigned long long* out, hipStream_t st);
 }  // namespace quad

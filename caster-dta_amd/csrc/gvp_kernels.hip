@@ -1,18 +1,21 @@
-// gvp_kernels.hip -- gfx950 kernels and the C ABI of libcaster_gvp.so
-// (declarations and reference citations: include/caster_gvp.h).
-//
-// Mapping (round 1): one residue / one edge per lane, 64-lane workgroups.
-//   * conv: a workgroup owns `npw` consecutive TARGET nodes (dst-sorted CSR), so
-//     the rows it reduces into are private: messages go lane -> LDS, a
-//     segmented reduction over the sorted targets runs in LDS, and the finished
-//     [npw][28] block is written with coalesced stores -- no atomics, no
-//     zero-fill, bitwise reproducible.  The raw edge features stream through
-//     the edge-embedding GVP + LayerNorm in registers (never materialised).
-//   * node kernels: row-per-lane, outputs transposed through LDS so global
-//     stores are contiguous.
+// gvp_kernels.hip -- three parts of libcaster_gvp.so (declarations and reference citations: include/caster_gvp.h):
+//   * the round-1 one-item-per-lane kernels (node_embed, conv_fwd, node_update, gine_conv): what the fine-grained forward
+//     entry points run when the caller passes no fragment image;
+//   * the dropout plumbing (cgvp_rng checks, rng_next_kernel, dropout_masks_kernel);
+//   * the fine-grained C ABI: each entry point validates its arguments, then dispatches to the tile kernels behind
+//     namespace quad (gvp_internal.h) or to the kernels of this file.
+// The CSR build, source-order index, collate and zero fill: graph_index_kernels.hip.  Whole passes: pass_api.hip.
+// Mapping of the one-item-per-lane kernels: one residue / one edge per lane, 64-lane workgroups.
+//   * conv: a workgroup owns `npw` consecutive TARGET nodes (dst-sorted CSR), so the rows it reduces into are private:
+//     messages go lane -> LDS, a segmented reduction over the sorted targets runs in LDS, and the finished [npw][28]
+//     block is written with coalesced stores -- no atomics, no zero-fill, bitwise reproducible.  The raw edge features
+//     stream through the edge-embedding GVP + LayerNorm in registers (never materialised).
+//   * node kernels: row-per-lane, outputs transposed through LDS so global stores are contiguous.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <stdint.h>
+
+#include <initializer_list>
 
 #include "gvp_internal.h"
 
@@ -53,10 +56,20 @@ inline EncLayout cvt(const cgvp_layout& l) {
   return L;
 }
 
+// one of the pointers is not 16-byte aligned (float4 row accesses); NULL passes: most of these buffers are optional
+inline bool misaligned16(std::initializer_list<const void*> ptrs) {
+  for (const void* q : ptrs) if ((uintptr_t)q & 15) return true;
+  return false;
+}
+
+// float offsets of the layout's slices inside the fragment image
+inline int image_offsets(const cgvp_layout& l, QuadOffsets* o) {
+  return quad::offsets(l.nt_node, l.nt_edge, num_convs_of(l), o);
+}
 // what every fine-grained backward entry point looks up first: the image offsets and the slab row sizes of the layout
 struct BwdLookup : QuadOffsets { quad::BwdBlocks blk; };
 inline int bwd_lookup(const cgvp_layout& l, BwdLookup* o) {
-  if (int rc = quad::offsets(l.nt_node, l.nt_edge, num_convs_of(l), o)) return rc;
+  if (int rc = image_offsets(l, o)) return rc;
   return quad::bwd_block_sizes(l.nt_node, l.nt_edge, &o->blk);
 }
 // ... and what it ends with: the slab segments go to the caller (who reduces them with the rest of the pass) or are
@@ -66,275 +79,6 @@ inline int emit_segments(const cgvp_segment* sg, int n, cgvp_segment* segs, int3
   if (segs && nsegs) { for (int k = 0; k < n; ++k) segs[k] = sg[k]; *nsegs = n; }
   else quad::reduce_segments(sg, n, grad_params, st, overwrite, store_only);
   return launch_status();
-}
-
-// ------------------------------------------------------------------ CSR build
-// Stable counting sort of the edges by target in four launches:
-//   count  : cnt[dst] += 1                                     (int atomics, one thread per edge)
-//   scan   : exclusive scan of cnt -> rowptr; cnt is left as it is     (N <= 64k: independent 1024-entry workgroups, each
-//            sums the counts before its chunk itself; longer tables: ONE block, LDS tiles with a carry)
-//   fill   : pos = rowptr[dst] + --cnt[dst] -> tmp[pos] = edge id, edst[pos] = dst   (reverse arrival order inside a
-//            segment; the counters count back down to the all-zero state the next call expects)
-//   rank   : every position ranks its edge id inside its segment (deg reads, all independent) and writes
-//            eperm / esrc at the ranked position: segments end up ordered by edge id = the reference's index_add
-//            order, run-to-run reproducible; the same launch zeroes the counters again for the next call.
-// Zero fill by a kernel of our own.  hipMemsetAsync is NOT used anywhere in this library: captured into a HIP graph, a
-// memset of a size that is not a multiple of 256 B (the runtime splits it into body + tail fills) left the buffer
-// un-zeroed on the second and later replays on this ROCm build (round 2: the GINE input gradients turned into garbage from
-// replay 1 on; tests/test_hip_models.py::test_joint_training_step_replays_from_a_hip_graph).
-__global__ void zero_words_kernel(uint32_t* __restrict__ p, size_t n) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = 0u;
-}
-inline void zero_words(void* p, size_t words, hipStream_t s) {
-  if (words == 0 || !p) return;
-  size_t blocks = (words + 1023) / 1024;                     // 4 words per thread at most
-  if (blocks > 2048) blocks = 2048;
-  launch<zero_words_kernel>(dim3((unsigned)blocks), dim3(256), 0, s, reinterpret_cast<uint32_t*>(p), words);
-}
-
-__global__ void csr_count_kernel(const int64_t* __restrict__ ei, int64_t N, int64_t E,
-                                 int32_t* __restrict__ cnt, unsigned long long* rng_state, unsigned long long* rng_out) {
-  int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (rng_state && e == 0) {             // optional: advance the persistent dropout generator (cgvp_rng_next's work)
-    const unsigned long long off = rng_state[1] + 1;
-    rng_state[1] = off;
-    rng_out[0] = rng_state[0];
-    rng_out[1] = off;
-  }
-  if (e >= E) return;
-  int64_t s = ei[e], d = ei[E + e];
-  if (s < 0 || s >= N || d < 0 || d >= N) return;   // malformed edge: dropped, never faults
-  atomicAdd(&cnt[d], 1);
-}
-
-// Exclusive scan of cnt[0..N) by ONE 1024-thread block; rowptr[N] = total.  The table goes through LDS in tiles of
-// SCAN_LDS entries (coalesced global traffic both ways) with a running carry, so long tables cost tiles x the
-// short-table time, not a strided crawl.  Tables of at most SCAN_MULTI_MAX entries take csr_scan_multi_kernel below.
-constexpr int SCAN_LDS = 36 * 1024;   // 144 KB of the 160 KB LDS
-__global__ __launch_bounds__(1024) void csr_scan_kernel(const int32_t* __restrict__ cnt, int64_t N,
-                                                        int32_t* __restrict__ rowptr) {
-  extern __shared__ int32_t sbuf[];             // [tile][1024 partials + 32]
-  const int t = threadIdx.x;
-  const int tile_cap = (int)(N < SCAN_LDS ? (N + 3) / 4 * 4 : SCAN_LDS);
-  int32_t* part = sbuf + tile_cap;
-  int32_t carry = 0;
-  for (int64_t base = 0; base < N || base == 0; base += SCAN_LDS) {
-    const int64_t rem = N - base;
-    const int n = (int)(rem < SCAN_LDS ? (rem > 0 ? rem : 0) : SCAN_LDS);     // entries of this tile
-    // all global loads in flight at once (9 x int4 per thread covers SCAN_LDS), then LDS
-    constexpr int VPT = SCAN_LDS / 4096;
-    int4 v[VPT];
-    const int n4 = n >> 2;
-    const int4* src4 = reinterpret_cast<const int4*>(cnt + base);     // base is a multiple of SCAN_LDS: 16-B aligned
-#pragma unroll
-    for (int k = 0; k < VPT; ++k) {
-      const int q = t + 1024 * k;
-      v[k] = q < n4 ? src4[q] : make_int4(0, 0, 0, 0);
-    }
-#pragma unroll
-    for (int k = 0; k < VPT; ++k) {
-      const int q = t + 1024 * k;
-      if (q < n4) reinterpret_cast<int4*>(sbuf)[q] = v[k];
-    }
-    if (t < (n & 3)) sbuf[(n4 << 2) + t] = cnt[base + (n4 << 2) + t];
-    __syncthreads();
-    const int chunk = (n + 1023) / 1024;
-    const int lo = t * chunk < n ? t * chunk : n, hi = lo + chunk < n ? lo + chunk : n;
-    int32_t sum = 0;
-    for (int i = lo; i < hi; ++i) sum += sbuf[i];
-    // inclusive scan of the 1024 per-thread sums: shuffles inside each wave, the 16 wave totals through
-    // LDS (2 barriers instead of the 20 of a block-wide Hillis-Steele)
-    int32_t inc = sum;
-#pragma unroll
-    for (int off = 1; off < WAVE; off <<= 1) {
-      const int32_t u = __shfl_up(inc, off);
-      if ((t & (WAVE - 1)) >= off) inc += u;
-    }
-    if ((t & (WAVE - 1)) == WAVE - 1) part[t >> 6] = inc;
-    __syncthreads();
-    if (t < 16) {
-      int32_t w = part[t];
-#pragma unroll
-      for (int off = 1; off < 16; off <<= 1) {
-        const int32_t u = __shfl_up(w, off, 16);
-        if (t >= off) w += u;
-      }
-      part[16 + t] = w;            // inclusive totals of waves 0..t
-    }
-    __syncthreads();
-    const int32_t wave_base = (t >> 6) > 0 ? part[16 + (t >> 6) - 1] : 0;
-    const int32_t total = part[31];
-    int32_t run = carry + wave_base + inc - sum;   // exclusive prefix of this thread's chunk
-    for (int i = lo; i < hi; ++i) { const int32_t c = sbuf[i]; sbuf[i] = run; run += c; }
-    __syncthreads();
-    if ((((uintptr_t)(rowptr + base)) & 15) == 0) {                   // 16-B stores (the usual case: allocator-aligned rowptr)
-      for (int q = t; q < n4; q += 1024) {
-        const int4 x = reinterpret_cast<const int4*>(sbuf)[q];
-        reinterpret_cast<int4*>(rowptr + base)[q] = x;
-      }
-      if (t < (n & 3)) rowptr[base + (n4 << 2) + t] = sbuf[(n4 << 2) + t];
-    } else {
-      for (int i = t; i < n; i += 1024) rowptr[base + i] = sbuf[i];
-    }
-    carry += total;
-    __syncthreads();
-    if (N == 0) break;
-  }
-  if (t == 0) rowptr[N] = carry;
-}
-
-// The scan for tables of at most SCAN_MULTI_MAX entries (every batch of the benchmark configs but the long-graph one):
-// workgroup b owns entries [1024 b, 1024 b + 1024) and gets the sum of everything before them by reading those counts
-// itself (<= 64 int4 per thread, all L2 hits) -- no carry chain between workgroups, no second launch, ~1/1024 of the
-// quadratic cost.  256-thread workgroups on purpose: the drug encoder's build runs on a side stream beside the protein
-// encoder's CU-filling kernels, and a 1024-thread / 4-waves-per-SIMD block found no CU to start on until those had
-// drained (59 us gap in the first round-4 step trace); one wave per SIMD fits beside them.
-// `cnt` holds `counters` (a multiple of 64, > N) zero-initialised words: entries N.. are zero, so rowptr[N] = total
-// falls out of the same exclusive scan.
-constexpr int SCAN_MULTI_MAX = 65536, SCAN_MULTI_T = 256, SCAN_MULTI_CHUNK = 4 * SCAN_MULTI_T;
-__global__ __launch_bounds__(SCAN_MULTI_T) void csr_scan_multi_kernel(const int32_t* __restrict__ cnt, int32_t N,
-                                                                      int32_t counters, int32_t* __restrict__ rowptr) {
-  __shared__ int32_t part[2 * (SCAN_MULTI_T / WAVE)];
-  const int t = threadIdx.x, wv = t >> 6;
-  const int4* c4 = reinterpret_cast<const int4*>(cnt);             // `work` is 16-B aligned (csr_build checks)
-  int32_t pre = 0;
-  for (int q = t; q < (int)blockIdx.x * SCAN_MULTI_T; q += SCAN_MULTI_T) {
-    const int4 v = c4[q];
-    pre += (v.x + v.y) + (v.z + v.w);
-  }
-  const int i0 = (int)blockIdx.x * SCAN_MULTI_CHUNK + 4 * t;
-  const int4 v = i0 < counters ? c4[i0 >> 2] : make_int4(0, 0, 0, 0);
-  const int32_t sum = (v.x + v.y) + (v.z + v.w);
-  int32_t inc = sum;
-#pragma unroll
-  for (int off = 1; off < WAVE; off <<= 1) {
-    const int32_t u = __shfl_up(inc, off);
-    if ((t & (WAVE - 1)) >= off) inc += u;
-    pre += __shfl_xor(pre, off);
-  }
-  if ((t & (WAVE - 1)) == WAVE - 1) { part[wv] = inc; part[SCAN_MULTI_T / WAVE + wv] = pre; }
-  __syncthreads();
-  int32_t run = inc - sum;                         // exclusive prefix of this thread's four entries
-#pragma unroll
-  for (int w = 0; w < SCAN_MULTI_T / WAVE; ++w) {
-    run += part[SCAN_MULTI_T / WAVE + w];
-    if (w < wv) run += part[w];
-  }
-  const int32_t x[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if (i0 + k <= N) rowptr[i0 + k] = run;
-    run += x[k];
-  }
-}
-
-__global__ void csr_fill_kernel(const int64_t* __restrict__ ei, int64_t N, int64_t E, const int32_t* __restrict__ rowptr,
-                                int32_t* __restrict__ cnt, int32_t* __restrict__ tmp, int32_t* __restrict__ edst) {
-  int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= E) return;
-  int64_t s = ei[e], d = ei[E + e];
-  if (s < 0 || s >= N || d < 0 || d >= N) return;
-  int32_t pos = rowptr[d] + atomicSub(&cnt[d], 1) - 1;
-  // pos < E always holds when the counters were zero on entry (the contract).  The guard makes a violated contract a wrong
-  // table instead of a wild write: round 2's recorded GPU fault ("write access to a read-only page" on replay of a captured
-  // step) was exactly this store -- the counters were then zero-filled by a captured hipMemsetAsync, which zeroes only
-  // part of its range from the second graph replay on (tools/memset_capture_probe.py), so counts accumulated over replays
-  // and `pos` ran past the E-element tables.
-  if (pos < 0 || pos >= E) return;
-  tmp[pos] = (int32_t)e;
-  edst[pos] = (int32_t)d;
-}
-
-// Position p of target n's segment holds SOME edge of n (arrival order of the fill).  Its final place is its rank
-// among the segment's edge ids; deg independent reads per position instead of a serial per-node insertion sort.
-// Threads t < counters also restore the zeroed-counters contract of `work`.
-// Positions rowptr[N] .. E of the sorted tables exist only when edges were dropped (endpoint out of range): they get
-// eperm = -1, esrc = edst = 0, so a kernel that walks all E positions (the edge-embedding backward) can skip them.
-__global__ void csr_rank_kernel(const int64_t* __restrict__ ei, int64_t N, int64_t E, int64_t counters,
-                                const int32_t* __restrict__ rowptr, const int32_t* __restrict__ tmp,
-                                int32_t* __restrict__ edst, int32_t* __restrict__ eperm,
-                                int32_t* __restrict__ esrc, int32_t* __restrict__ cnt) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < counters) cnt[t] = 0;
-  if (t >= rowptr[N] || t >= E) {
-    if (t < E) { eperm[t] = -1; esrc[t] = 0; edst[t] = 0; }
-    return;
-  }
-  // (the range checks below never fire on tables built from zeroed counters; they keep every access inside the
-  // E-element tables whatever the counters held -- see csr_fill_kernel)
-  const int32_t n = edst[t];
-  if (n < 0 || n >= N) return;
-  int32_t lo = rowptr[n], hi = rowptr[n + 1];
-  const int32_t key = tmp[t];
-  if (lo < 0 || hi > E || lo > hi || key < 0 || key >= E) return;
-  int32_t rank = 0;
-  for (int32_t j = lo; j < hi; ++j) rank += tmp[j] < key ? 1 : 0;
-  eperm[lo + rank] = key;
-  esrc[lo + rank] = (int32_t)ei[key];
-}
-
-// ===================================================================== source-order index (deterministic mode)
-// The sorted positions of every SOURCE of a dst-sorted CSR, in increasing position: the read-back order of the per-source
-// sums that replace the d h[src] / d x[src] float atomics (quad::src_sum).  Count / scan / fill as in the CSR build
-// (integer atomics: only the fill order depends on arrival), then each position's rank among its source's positions
-// fixes the order.  The fill counts the counters back down to zero.
-__global__ void src_count_kernel(const int32_t* __restrict__ esrc, const int32_t* __restrict__ rowptr, int64_t N,
-                                 int32_t* __restrict__ cnt) {
-  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= rowptr[N]) return;
-  const int32_t s = esrc[p];
-  if (s >= 0 && s < N) atomicAdd(&cnt[s], 1);
-}
-__global__ void src_fill_kernel(const int32_t* __restrict__ esrc, const int32_t* __restrict__ rowptr, int64_t N,
-                                const int32_t* __restrict__ sptr, int32_t* __restrict__ cnt, int32_t* __restrict__ tmp) {
-  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int32_t ev = rowptr[N];
-  if (p >= ev) return;
-  const int32_t s = esrc[p];
-  if (s < 0 || s >= N) return;
-  const int32_t pos = sptr[s] + atomicSub(&cnt[s], 1) - 1;
-  if (pos >= 0 && pos < ev) tmp[pos] = (int32_t)p;
-}
-__global__ void src_rank_kernel(const int32_t* __restrict__ esrc, const int32_t* __restrict__ rowptr, int64_t N,
-                                const int32_t* __restrict__ sptr, const int32_t* __restrict__ tmp, int32_t* __restrict__ spos) {
-  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int32_t ev = rowptr[N];
-  if (k >= ev) return;
-  const int32_t p = tmp[k];
-  if (p < 0 || p >= ev) return;
-  const int32_t s = esrc[p];
-  if (s < 0 || s >= N) return;
-  const int32_t lo = sptr[s], hi = sptr[s + 1];
-  if (lo < 0 || hi > ev || lo > hi) return;
-  int32_t rank = 0;
-  for (int32_t j = lo; j < hi; ++j) rank += tmp[j] < p ? 1 : 0;
-  spos[lo + rank] = p;
-}
-
-// Batch CSR by CONCATENATION of per-graph CSRs (a dataset's few hundred unique
-// graphs are sorted once; a batch is their blocks shifted by node / edge offsets).  One workgroup
-// per batch slot; `sel[b]` is the slot's graph in the store, whose tables hold LOCAL indices.
-struct CsrCollateArgs {
-  const int32_t* st_rowptr; const int32_t* st_eperm; const int32_t* st_esrc; const int32_t* st_edst;
-  const int64_t* st_node_off; const int64_t* st_edge_off;      // [G+1] prefix sums over the store's graphs
-  const int64_t* sel; const int64_t* b_node_off; const int64_t* b_edge_off;   // [B], [B+1], [B+1]
-  int64_t B; int32_t* rowptr; int32_t* eperm; int32_t* esrc; int32_t* edst;
-  int table_mode;      // 1: eperm = position in the STORE's dst-sorted feature tables (features stay resident, read in place)
-};
-__global__ __launch_bounds__(256) void csr_collate_kernel(CsrCollateArgs a) {
-  const int64_t b = blockIdx.x;
-  const int64_t g = a.sel[b];
-  const int64_t sn = a.st_node_off[g], se = a.st_edge_off[g];
-  const int64_t n = a.st_node_off[g + 1] - sn, e = a.st_edge_off[g + 1] - se;
-  const int64_t bn = a.b_node_off[b], be = a.b_edge_off[b];
-  const int32_t* rp = a.st_rowptr + sn + g;                     // every graph stores n + 1 row pointers
-  for (int64_t k = threadIdx.x; k < n; k += 256) a.rowptr[bn + k] = (int32_t)(be + rp[k]);
-  if (b == a.B - 1 && threadIdx.x == 0) a.rowptr[bn + n] = (int32_t)(be + e);
-  for (int64_t k = threadIdx.x; k < e; k += 256) {
-    a.eperm[be + k] = a.table_mode ? (int32_t)(se + k) : (int32_t)(be + a.st_eperm[se + k]);
-    a.esrc[be + k] = (int32_t)(bn + a.st_esrc[se + k]);
-    a.edst[be + k] = (int32_t)(bn + a.st_edst[se + k]);
-  }
 }
 
 // Launder the arena pointer through an empty asm so the optimiser cannot hoist
@@ -673,10 +417,9 @@ static int check_rng(const cgvp_rng* rng) {
   if (!(rng->p >= 0.f && rng->p < 1.f) || rng->stream < 0 || ((uintptr_t)rng->seed & 7)) return CGVP_ERR_BAD_ARG;
   return 0;
 }
-// kernel-argument form; `base` = the stream the entry point's convention assigns when the caller leaves it 0
-static gvp::RngArgs rng_args(const cgvp_rng* rng, int base) {
+// kernel-argument form
+static gvp::RngArgs rng_args(const cgvp_rng* rng) {
   if (!rng || !rng->seed) return gvp::RngArgs{nullptr, 0.f, 0};
-  (void)base;
   return gvp::RngArgs{reinterpret_cast<const unsigned long long*>(rng->seed), rng->p, rng->stream};
 }
 
@@ -685,6 +428,10 @@ __global__ void rng_next_kernel(unsigned long long* state, unsigned long long* o
   state[1] = off;
   out[0] = state[0];
   out[1] = off;
+}
+// cgvp_rng_next without its checks (the CSR build calls it when it has no count launch to advance the generator in)
+int quad::rng_next(unsigned long long* state, unsigned long long* out, hipStream_t st) {
+  return launch<rng_next_kernel>(dim3(1), dim3(1), 0, st, state, out);
 }
 
 struct MaskArgs { gvp::RngArgs rng; int num_masks; int64_t N; int width; float* out; };
@@ -710,107 +457,18 @@ __global__ __launch_bounds__(256) void dropout_masks_kernel(MaskArgs a) {
   }
 }
 
+bool quad::deterministic_env() {
+  static const bool v = [] { const char* e = getenv("CGVP_DETERMINISTIC"); return e && e[0] == '1'; }();
+  return v;
+}
+
 // ===================================================================== C ABI
 extern "C" {
 
 int cgvp_abi_version(void) { return CGVP_ABI_VERSION; }
 const char* cgvp_build_info(void) { return "libcaster_gvp gfx950 (HIP, wave64), built " __DATE__ " " __TIME__; }
 
-int cgvp_csr_from_coo(const int64_t* edge_index, int64_t N, int64_t E, int32_t* rowptr,
-                      int32_t* eperm, int32_t* esrc, int32_t* edst, int32_t* work, int32_t work_is_zero,
-                      int32_t* ids_scratch, void* stream) {
-  return quad::csr_build(edge_index, N, E, rowptr, eperm, esrc, edst, work, work_is_zero, ids_scratch, nullptr, nullptr,
-                         (hipStream_t)stream);
-}
-}  // extern "C"
-
-namespace quad {
-void zero_words(void* p, size_t words, hipStream_t s) { ::zero_words(p, words, s); }
-
-// cgvp_csr_from_coo; rng_state / rng_out (both or neither): the count launch also advances the dropout generator
-// (cgvp_rng_next's work) -- with E == 0 or work_is_zero == 2 there is no count launch and a 1-thread launch does it.
-int csr_build(const int64_t* edge_index, int64_t N, int64_t E, int32_t* rowptr, int32_t* eperm, int32_t* esrc,
-              int32_t* edst, int32_t* work, int work_is_zero, int32_t* ids_scratch, unsigned long long* rng_state,
-              unsigned long long* rng_out, hipStream_t stream) {
-  if (N < 0 || E < 0 || !rowptr || !work || (E > 0 && (!edge_index || !eperm || !esrc || !edst || !ids_scratch)))
-    return CGVP_ERR_BAD_ARG;
-  if (N >= (int64_t)1 << 31 || E >= (int64_t)1 << 31) return CGVP_ERR_BAD_ARG;
-  if ((uintptr_t)work & 15) return CGVP_ERR_BAD_ARG;
-  hipStream_t s = stream;
-  const int64_t counters = (N + 1 + 63) / 64 * 64;
-  if (work_is_zero == 0) {
-    zero_words(work, (size_t)counters, s);
-  }
-  int32_t* tmp = ids_scratch;
-  const int B = 256;
-  if (E > 0 && work_is_zero != 2)     // 2: cgvp_lba_pass_begin already counted into `work`
-    launch<csr_count_kernel>(dim3((unsigned)((E + B - 1) / B)), dim3(B), 0, s, edge_index, N, E, work, rng_state, rng_out);
-  else if (rng_state)
-    launch<rng_next_kernel>(dim3(1), dim3(1), 0, s, rng_state, rng_out);
-  if (N < SCAN_MULTI_MAX) {
-    launch<csr_scan_multi_kernel>(dim3((unsigned)((N + 1 + SCAN_MULTI_CHUNK - 1) / SCAN_MULTI_CHUNK)),
-                                  dim3(SCAN_MULTI_T), 0, s, work, (int32_t)N, (int32_t)counters, rowptr);
-  } else {
-    const int64_t tile = N < SCAN_LDS ? (N + 3) / 4 * 4 : SCAN_LDS;
-    if (int rc = launch<csr_scan_kernel>(dim3(1), dim3(1024), (size_t)(tile + 1024 + 32) * sizeof(int32_t), s, work, N, rowptr)) return rc;
-  }
-  if (E > 0) launch<csr_fill_kernel>(dim3((unsigned)((E + B - 1) / B)), dim3(B), 0, s, edge_index, N, E, rowptr, work, tmp, edst);
-  const int64_t span = E > counters ? E : counters;
-  launch<csr_rank_kernel>(dim3((unsigned)((span + B - 1) / B)), dim3(B), 0, s, edge_index, N, E, counters, rowptr, tmp,
-                          edst, eperm, esrc, work);
-  return launch_status();
-}
-
-bool deterministic_env() {
-  static const bool v = [] { const char* e = getenv("CGVP_DETERMINISTIC"); return e && e[0] == '1'; }();
-  return v;
-}
-
-// work: [counters (N + 1 rounded up to 64) | tmp (E)]
-int64_t src_index_work_ints(int64_t N, int64_t E) { return (N + 1 + 63) / 64 * 64 + (E > 0 ? E : 1); }
-
-int src_index(const int32_t* rowptr, const int32_t* esrc, int64_t N, int64_t E, int32_t* sptr, int32_t* spos,
-              int32_t* work, hipStream_t s) {
-  if (N < 0 || E < 0 || !rowptr || !sptr || !work || (E > 0 && (!esrc || !spos))) return CGVP_ERR_BAD_ARG;
-  if (N >= (int64_t)1 << 31 || E >= (int64_t)1 << 31 || ((uintptr_t)work & 15)) return CGVP_ERR_BAD_ARG;
-  const int64_t counters = (N + 1 + 63) / 64 * 64;
-  int32_t* cnt = work;
-  int32_t* tmp = work + counters;
-  zero_words(cnt, (size_t)counters, s);
-  const int B = 256;
-  const unsigned eb = (unsigned)((E + B - 1) / B);
-  if (E > 0) launch<src_count_kernel>(dim3(eb), dim3(B), 0, s, esrc, rowptr, N, cnt);
-  if (N < SCAN_MULTI_MAX) {
-    launch<csr_scan_multi_kernel>(dim3((unsigned)((N + 1 + SCAN_MULTI_CHUNK - 1) / SCAN_MULTI_CHUNK)),
-                                  dim3(SCAN_MULTI_T), 0, s, cnt, (int32_t)N, (int32_t)counters, sptr);
-  } else {
-    const int64_t tile = N < SCAN_LDS ? (N + 3) / 4 * 4 : SCAN_LDS;
-    if (int rc = launch<csr_scan_kernel>(dim3(1), dim3(1024), (size_t)(tile + 1024 + 32) * sizeof(int32_t), s, cnt, N, sptr)) return rc;
-  }
-  if (E > 0) {
-    launch<src_fill_kernel>(dim3(eb), dim3(B), 0, s, esrc, rowptr, N, sptr, cnt, tmp);
-    launch<src_rank_kernel>(dim3(eb), dim3(B), 0, s, esrc, rowptr, N, sptr, tmp, spos);
-  }
-  return launch_status();
-}
-}  // namespace quad
-
-extern "C" {
-
 int cgvp_deterministic_forced(void) { return quad::deterministic_env() ? 1 : 0; }
-
-int cgvp_csr_collate(const int32_t* st_rowptr, const int32_t* st_eperm, const int32_t* st_esrc,
-                     const int32_t* st_edst, const int64_t* st_node_off, const int64_t* st_edge_off,
-                     const int64_t* sel, const int64_t* b_node_off, const int64_t* b_edge_off, int64_t B,
-                     int32_t table_mode, int32_t* rowptr, int32_t* eperm, int32_t* esrc, int32_t* edst, void* stream) {
-  if (B < 0 || !rowptr) return CGVP_ERR_BAD_ARG;
-  if (B == 0) return 0;
-  if (!st_rowptr || !st_node_off || !st_edge_off || !sel || !b_node_off || !b_edge_off) return CGVP_ERR_BAD_ARG;
-  CsrCollateArgs a{st_rowptr, st_eperm, st_esrc, st_edst, st_node_off, st_edge_off, sel, b_node_off, b_edge_off, B,
-                   rowptr, eperm, esrc, edst, table_mode ? 1 : 0};
-  launch<csr_collate_kernel>(dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, a);
-  return launch_status();
-}
 
 int cgvp_lba_layout(const cgvp_dims* dims, int32_t num_ntypes, int32_t num_etypes, int32_t num_convs,
                     cgvp_layout* out) {
@@ -827,7 +485,7 @@ int64_t cgvp_lba_image_floats(const cgvp_dims* dims, const cgvp_layout* layout) 
   if (int rc = check_dims(dims)) return rc;
   if (!layout) return CGVP_ERR_BAD_ARG;
   QuadOffsets o;
-  if (int rc = quad::offsets(layout->nt_node, layout->nt_edge, num_convs_of(*layout), &o)) return rc;
+  if (int rc = image_offsets(*layout, &o)) return rc;
   return o.total;
 }
 
@@ -847,7 +505,7 @@ int cgvp_lba_pass_begin(const cgvp_dims* dims, const cgvp_layout* layout, const 
   if (int rc = check_dims_gated(dims)) return rc;
   if (N < 0 || E < 0 || !layout || !params || !image || (layout->nt_node > 0 && N > 0 && !ntypes)) return CGVP_ERR_BAD_ARG;
   if ((rng_state != nullptr) != (rng_out != nullptr)) return CGVP_ERR_BAD_ARG;
-  if (((uintptr_t)rng_state & 7) || ((uintptr_t)rng_out & 7) || ((uintptr_t)h & 15) || ((uintptr_t)image & 15)) return CGVP_ERR_BAD_ARG;
+  if (((uintptr_t)rng_state & 7) || ((uintptr_t)rng_out & 7) || misaligned16({h, image})) return CGVP_ERR_BAD_ARG;
   if ((edge_index != nullptr) != (csr_counters != nullptr)) return CGVP_ERR_BAD_ARG;
   if (N > 0 && (!x_s || !x_v || !h)) return CGVP_ERR_BAD_ARG;
   if (N >= (int64_t)1 << 31 || E >= (int64_t)1 << 31) return CGVP_ERR_BAD_ARG;
@@ -859,7 +517,6 @@ int cgvp_lba_pass_begin(const cgvp_dims* dims, const cgvp_layout* layout, const 
   return launch_status();
 }
 
-
 int cgvp_node_embed_fwd(const cgvp_dims* dims, const cgvp_layout* layout, const float* params,
                         const float* image, const float* x_s, const float* x_v, const int64_t* ntypes,
                         int64_t N, float* h, uint64_t* rng_state, uint64_t* rng_out, void* stream) {
@@ -870,9 +527,9 @@ int cgvp_node_embed_fwd(const cgvp_dims* dims, const cgvp_layout* layout, const 
   if (N == 0) return rng_state ? cgvp_rng_next(rng_state, rng_out, stream) : 0;
   if (!x_s || !x_v || !h) return CGVP_ERR_BAD_ARG;
   if (image) {
-    if ((uintptr_t)h & 15) return CGVP_ERR_BAD_ARG;
+    if (misaligned16({h})) return CGVP_ERR_BAD_ARG;
     QuadOffsets o;
-    if (int rc = quad::offsets(layout->nt_node, layout->nt_edge, num_convs_of(*layout), &o)) return rc;
+    if (int rc = image_offsets(*layout, &o)) return rc;
     if (int rc = quad::node_embed(layout->nt_node, image + o.emb, x_s, x_v, ntypes, N, h,
                                   reinterpret_cast<unsigned long long*>(rng_state),
                                   reinterpret_cast<unsigned long long*>(rng_out), policy_of(dims), (hipStream_t)stream)) return rc;
@@ -905,10 +562,10 @@ int cgvp_conv_fwd(const cgvp_dims* dims, const cgvp_layout* layout, const float*
   if (!image && (e_in || e_out)) return CGVP_ERR_BAD_ARG;      // the stored edge embedding is a feature of the MFMA kernels
   if (E > 0 && (!esrc || !edst)) return CGVP_ERR_BAD_ARG;
   if (E > 0 && !e_in && (!e_s || !e_v || !eperm || (layout->nt_edge > 0 && !etypes))) return CGVP_ERR_BAD_ARG;
-  if (((uintptr_t)h & 15) || ((uintptr_t)e_s & 15) || ((uintptr_t)e_in & 15) || ((uintptr_t)e_out & 15)) return CGVP_ERR_BAD_ARG;   // float4 row loads
+  if (misaligned16({h, e_s, e_in, e_out})) return CGVP_ERR_BAD_ARG;   // float4 row loads
   if (image) {
     QuadOffsets o;
-    if (int rc = quad::offsets(layout->nt_node, layout->nt_edge, num_convs_of(*layout), &o)) return rc;
+    if (int rc = image_offsets(*layout, &o)) return rc;
     if (int rc = quad::conv(layout->nt_edge, image + o.conv0 + layer * o.layer_stride, h, e_s, e_v, etypes, rowptr,
                             eperm, esrc, edst, N, E, aggr_mean ? 1 : 0, dh, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
                             nullptr, gvp::RngArgs{nullptr, 0.f, 0}, e_in, e_in ? nullptr : e_out, policy_of(dims),
@@ -947,14 +604,13 @@ int cgvp_conv_layer_fwd(const cgvp_dims* dims, const cgvp_layout* layout, const 
   if (!h || !rowptr || (with_head ? !out : !h_out)) return CGVP_ERR_BAD_ARG;
   if (E > 0 && (!esrc || !edst)) return CGVP_ERR_BAD_ARG;
   if (E > 0 && !e_in && (!e_s || !e_v || !eperm || (layout->nt_edge > 0 && !etypes))) return CGVP_ERR_BAD_ARG;
-  const void* al[] = {h, e_s, dh, h_out, out, mask0, mask1, e_in, e_out};
-  for (const void* q : al) if ((uintptr_t)q & 15) return CGVP_ERR_BAD_ARG;
+  if (misaligned16({h, e_s, dh, h_out, out, mask0, mask1, e_in, e_out})) return CGVP_ERR_BAD_ARG;
   QuadOffsets o;
-  if (int rc = quad::offsets(layout->nt_node, layout->nt_edge, num_convs_of(*layout), &o)) return rc;
+  if (int rc = image_offsets(*layout, &o)) return rc;
   if (int rc = quad::conv(layout->nt_edge, image + o.conv0 + layer * o.layer_stride, h, e_s, e_v, etypes, rowptr, eperm,
                           esrc, edst, N, E, aggr_mean ? 1 : 0, dh, with_head ? 2 : 1,
                           image + o.node0 + layer * o.layer_stride, image + o.head, h_out, out, mask0, mask1,
-                          rng_args(rng, 2 * layer), e_in, e_in ? nullptr : e_out, policy_of(dims), (hipStream_t)stream)) return rc;
+                          rng_args(rng), e_in, e_in ? nullptr : e_out, policy_of(dims), (hipStream_t)stream)) return rc;
   return launch_status();
 }
 
@@ -966,11 +622,11 @@ int cgvp_node_update_fwd(const cgvp_dims* dims, const cgvp_layout* layout, const
   if (layer < 0 || layer >= num_convs_of(*layout)) return CGVP_ERR_BAD_ARG;
   if (N == 0) return 0;
   if (!h || !dh || (with_head ? !out : !h_out)) return CGVP_ERR_BAD_ARG;
-  if (((uintptr_t)h & 15) || ((uintptr_t)dh & 15)) return CGVP_ERR_BAD_ARG;
+  if (misaligned16({h, dh})) return CGVP_ERR_BAD_ARG;
   if (image) {
-    if (((uintptr_t)h_out & 15) || ((uintptr_t)out & 15)) return CGVP_ERR_BAD_ARG;
+    if (misaligned16({h_out, out})) return CGVP_ERR_BAD_ARG;
     QuadOffsets o;
-    if (int rc = quad::offsets(layout->nt_node, layout->nt_edge, num_convs_of(*layout), &o)) return rc;
+    if (int rc = image_offsets(*layout, &o)) return rc;
     if (int rc = quad::node_update(image + o.node0 + layer * o.layer_stride, image + o.head, h, dh, N,
                                    with_head ? 1 : 0, h_out, out, nullptr, nullptr, gvp::RngArgs{nullptr, 0.f, 0},
                                    policy_of(dims), (hipStream_t)stream)) return rc;
@@ -994,12 +650,11 @@ int cgvp_node_update_fwd_train(const cgvp_dims* dims, const cgvp_layout* layout,
   if (layer < 0 || layer >= num_convs_of(*layout)) return CGVP_ERR_BAD_ARG;
   if (N == 0) return 0;
   if (!h || !dh || (with_head ? !out : !h_out)) return CGVP_ERR_BAD_ARG;
-  if (((uintptr_t)h & 15) || ((uintptr_t)dh & 15) || ((uintptr_t)h_out & 15) || ((uintptr_t)out & 15) ||
-      ((uintptr_t)mask0 & 15) || ((uintptr_t)mask1 & 15)) return CGVP_ERR_BAD_ARG;
+  if (misaligned16({h, dh, h_out, out, mask0, mask1})) return CGVP_ERR_BAD_ARG;
   QuadOffsets o;
-  if (int rc = quad::offsets(layout->nt_node, layout->nt_edge, num_convs_of(*layout), &o)) return rc;
+  if (int rc = image_offsets(*layout, &o)) return rc;
   if (int rc = quad::node_update(image + o.node0 + layer * o.layer_stride, image + o.head, h, dh, N,
-                                 with_head ? 1 : 0, h_out, out, mask0, mask1, rng_args(rng, 2 * layer),
+                                 with_head ? 1 : 0, h_out, out, mask0, mask1, rng_args(rng),
                                  policy_of(dims), (hipStream_t)stream)) return rc;
   return launch_status();
 }
@@ -1029,8 +684,7 @@ int cgvp_node_update_bwd(const cgvp_dims* dims, const cgvp_layout* layout, const
   if (N == 0) return 0;
   if (!h || !dh || !g_dh || (with_head && (!g_out || !h_out))) return CGVP_ERR_BAD_ARG;
   if (with_head && dims->layer_kind != CGVP_LAYER_GATED) return CGVP_ERR_UNSUPPORTED_DIMS;     // the head is CASTER-DTA's
-  const void* al[] = {h, dh, mask0, mask1, h_out, g_out, g_up0, g_up1, g_up2, g_dh, g_h, zero_out};
-  for (const void* q : al) if ((uintptr_t)q & 15) return CGVP_ERR_BAD_ARG;
+  if (misaligned16({h, dh, mask0, mask1, h_out, g_out, g_up0, g_up1, g_up2, g_dh, g_h, zero_out})) return CGVP_ERR_BAD_ARG;
   BwdLookup o;
   if (int rc = bwd_lookup(*layout, &o)) return rc;
   int grid = 0, hgrid = 0;
@@ -1042,7 +696,7 @@ int cgvp_node_update_bwd(const cgvp_dims* dims, const cgvp_layout* layout, const
     // the head's d h_out lands in g_dh and is consumed in place as the node stage's upstream, inside ONE launch
     if (int rc = quad::node_head_bwd(image + o.head, image + o.headT, h_out, g_out, g_dh, head_slab,
                                      image + o.node0 + layer * o.layer_stride, image + o.nodeT0 + layer * o.layerT_stride,
-                                     h, dh, mask0, mask1, rng_args(rng, 2 * layer), N, g_dh, g_h, zero_out, workspace, &grid,
+                                     h, dh, mask0, mask1, rng_args(rng), N, g_dh, g_h, zero_out, workspace, &grid,
                                      policy_of(dims), st)) return rc;
     hgrid = grid;
   } else {
@@ -1051,7 +705,7 @@ int cgvp_node_update_bwd(const cgvp_dims* dims, const cgvp_layout* layout, const
     g_up0 = g_dh; g_up1 = nullptr; g_up2 = nullptr;
   }
   if (int rc = quad::node_update_bwd(image + o.node0 + layer * o.layer_stride, image + o.nodeT0 + layer * o.layerT_stride,
-                                     h, dh, mask0, mask1, rng_args(rng, 2 * layer), g_up0, g_up1, g_up2, N, g_dh, g_h, zero_out,
+                                     h, dh, mask0, mask1, rng_args(rng), g_up0, g_up1, g_up2, N, g_dh, g_h, zero_out,
                                      workspace, &grid, policy_of(dims), st)) return rc;
   }
   const int node_len = conv_ff1() + LFf1::size(0) - conv_ln0();          // norm.0 .. end of ff_func.1
@@ -1085,15 +739,12 @@ int quad::conv_bwd_entry(const cgvp_dims* dims, const cgvp_layout* layout, const
   if (N == 0) return 0;
   if (!h || !g_dh || !g_src || !g_dst || !rowptr) return CGVP_ERR_BAD_ARG;
   if (E > 0 && (!e_emb || !g_e || !esrc || !edst)) return CGVP_ERR_BAD_ARG;
-  const void* al[] = {h, e_emb, g_dh, g_src, g_dst, g_e};
-  for (const void* q : al) if ((uintptr_t)q & 15) return CGVP_ERR_BAD_ARG;
+  if (misaligned16({h, e_emb, g_dh, g_src, g_dst, g_e})) return CGVP_ERR_BAD_ARG;
   BwdLookup o;
   if (int rc = bwd_lookup(*layout, &o)) return rc;
   int grid = 0;
   hipStream_t st = (hipStream_t)stream;
-  if (!g_src_zeroed && !det) {
-    zero_words(g_src, (size_t)N * ROW, st);
-  }
+  if (!g_src_zeroed && !det) quad::zero_words(g_src, (size_t)N * ROW, st);
   if (int rc = quad::conv_bwd(layout->nt_edge, image + o.conv0 + layer * o.layer_stride,
                               image + o.convT0 + layer * o.layerT_stride, h, e_emb, rowptr, esrc, edst, N, E,
                               aggr_mean ? 1 : 0, g_dh, g_src, g_dst, g_e, workspace, &grid, policy_of(dims), st,
@@ -1106,16 +757,6 @@ int quad::conv_bwd_entry(const cgvp_dims* dims, const cgvp_layout* layout, const
 }
 
 extern "C" {
-
-int64_t cgvp_src_index_work_ints(int64_t num_nodes, int64_t num_edges) {
-  if (num_nodes < 0 || num_edges < 0) return CGVP_ERR_BAD_ARG;
-  return quad::src_index_work_ints(num_nodes, num_edges);
-}
-
-int cgvp_src_index(const int32_t* rowptr, const int32_t* esrc, int64_t num_nodes, int64_t num_edges, int32_t* sptr,
-                   int32_t* spos, int32_t* work, void* stream) {
-  return quad::src_index(rowptr, esrc, num_nodes, num_edges, sptr, spos, work, (hipStream_t)stream);
-}
 
 int64_t cgvp_conv_bwd_det_floats(int64_t num_nodes, int64_t num_edges) {
   if (num_nodes < 0 || num_edges < 0) return CGVP_ERR_BAD_ARG;
@@ -1131,15 +772,11 @@ int cgvp_conv_bwd_ex(const cgvp_dims* dims, const cgvp_layout* layout, const flo
   if (!((flags & CGVP_BWD_DETERMINISTIC) || quad::deterministic_env()))
     return quad::conv_bwd_entry(dims, layout, image, layer, h, e_emb, rowptr, esrc, edst, N, E, aggr_mean, g_dh, g_src,
                                 g_src_zeroed, g_dst, g_e, grad_params, workspace, segs, nsegs, stream, nullptr);
-  if (!sptr || !det_scratch || (E > 0 && !spos) || ((uintptr_t)det_scratch & 15)) return CGVP_ERR_BAD_ARG;
+  if (!sptr || !det_scratch || (E > 0 && !spos) || misaligned16({det_scratch})) return CGVP_ERR_BAD_ARG;
   const quad::DetBufs db{sptr, spos, det_scratch, det_scratch + (E > 0 ? E : 1) * ROW};
   return quad::conv_bwd_entry(dims, layout, image, layer, h, e_emb, rowptr, esrc, edst, N, E, aggr_mean, g_dh, g_src,
                               g_src_zeroed, g_dst, g_e, grad_params, workspace, segs, nsegs, stream, &db);
 }
-
-}  // extern "C"
-
-extern "C" {
 
 int cgvp_edge_embed_bwd(const cgvp_dims* dims, const cgvp_layout* layout, const float* image, const float* e_s,
                         const float* e_v, const int64_t* etypes, const int32_t* eperm, int64_t E,
@@ -1147,12 +784,12 @@ int cgvp_edge_embed_bwd(const cgvp_dims* dims, const cgvp_layout* layout, const 
                         float* workspace, cgvp_segment* segs, int32_t* nsegs, void* stream) {
   if (int rc = check_dims_gated(dims)) return rc;
   if (E < 0 || !layout || !image || !grad_params || !workspace || !g_e || num_g < 1) return CGVP_ERR_BAD_ARG;
-  if ((g_e_s == nullptr) != (g_e_v == nullptr) || ((uintptr_t)g_e_s & 15)) return CGVP_ERR_BAD_ARG;
+  if ((g_e_s == nullptr) != (g_e_v == nullptr) || misaligned16({g_e_s})) return CGVP_ERR_BAD_ARG;
   if (segs && nsegs) *nsegs = 0;
   if (E == 0) return 0;
   if (!e_s || !e_v || !eperm || (layout->nt_edge > 0 && !etypes)) return CGVP_ERR_BAD_ARG;
-  if ((uintptr_t)e_s & 15) return CGVP_ERR_BAD_ARG;
-  for (int l = 0; l < num_g; ++l) if (!g_e[l] || ((uintptr_t)g_e[l] & 15)) return CGVP_ERR_BAD_ARG;
+  if (misaligned16({e_s})) return CGVP_ERR_BAD_ARG;
+  for (int l = 0; l < num_g; ++l) if (!g_e[l] || misaligned16({g_e[l]})) return CGVP_ERR_BAD_ARG;
   BwdLookup o;
   if (int rc = bwd_lookup(*layout, &o)) return rc;
   int grid = 0;
@@ -1176,8 +813,7 @@ int cgvp_node_embed_bwd(const cgvp_dims* dims, const cgvp_layout* layout, const 
   if (N < 0 || !layout || !image || !grad_params || !workspace) return CGVP_ERR_BAD_ARG;
   if (N == 0) return 0;
   if (!x_s || !x_v || (layout->nt_node > 0 && !ntypes) || ((g_x_s == nullptr) != (g_x_v == nullptr))) return CGVP_ERR_BAD_ARG;
-  const void* al[] = {g_up0, g_up1, g_up2};
-  for (const void* q : al) if ((uintptr_t)q & 15) return CGVP_ERR_BAD_ARG;
+  if (misaligned16({g_up0, g_up1, g_up2})) return CGVP_ERR_BAD_ARG;
   BwdLookup o;
   if (int rc = bwd_lookup(*layout, &o)) return rc;
   int grid = 0;
@@ -1196,7 +832,7 @@ int cgvp_gine_conv_fwd(const float* x, const int64_t* ntypes, int32_t num_ntypes
                        void* stream) {
   if (N < 0 || E < 0 || !w) return CGVP_ERR_BAD_ARG;
   if (int rc = check_rng(rng)) return rc;
-  const gvp::RngArgs ra = rng_args(rng, 0);
+  const gvp::RngArgs ra = rng_args(rng);
   if (num_ntypes < 0 || num_etypes < 0 || edge_dim < 0 || cin <= num_ntypes) return CGVP_ERR_BAD_ARG;
   if (cin > WAVE || chid > WAVE || cout > WAVE || chid < 1 || cout < 1 || num_etypes + edge_dim > GINE_MAXKE)
     return CGVP_ERR_UNSUPPORTED_DIMS;
@@ -1205,7 +841,7 @@ int cgvp_gine_conv_fwd(const float* x, const int64_t* ntypes, int32_t num_ntypes
   if (E > 0 && (!eperm || !esrc || (edge_dim > 0 && !eattr) || (num_etypes > 0 && !etypes))) return CGVP_ERR_BAD_ARG;
   // variant 0: 16-atom MFMA tiles when the layer shape is compiled (needs edst and 16-B aligned
   // out / mask); variant 1 or any other shape: generic one-wave-per-atom kernel
-  if (variant == 0 && edst && !((uintptr_t)out & 15) && !((uintptr_t)mask & 15)) {
+  if (variant == 0 && edst && !misaligned16({out, mask})) {
     const int rc = quad::gine_fwd(cin, chid, cout, num_ntypes, num_etypes, edge_dim, x, ntypes, eattr, etypes, rowptr,
                                   eperm, esrc, edst, N, w, act_slope, mask, ra, out, nullptr, nullptr, (hipStream_t)stream);
     if (rc <= 0) return rc < 0 ? rc : launch_status();
@@ -1220,8 +856,7 @@ int cgvp_gine_conv_fwd(const float* x, const int64_t* ntypes, int32_t num_ntypes
 
 int cgvp_rng_next(uint64_t* state, uint64_t* out, void* stream) {
   if (!state || !out || ((uintptr_t)state & 7) || ((uintptr_t)out & 7)) return CGVP_ERR_BAD_ARG;
-  launch<rng_next_kernel>(dim3(1), dim3(1), 0, (hipStream_t)stream,
-                          reinterpret_cast<unsigned long long*>(state), reinterpret_cast<unsigned long long*>(out));
+  quad::rng_next(reinterpret_cast<unsigned long long*>(state), reinterpret_cast<unsigned long long*>(out), (hipStream_t)stream);
   return launch_status();
 }
 
@@ -1229,7 +864,7 @@ int cgvp_dropout_masks(const cgvp_rng* rng, int32_t num_masks, int64_t N, int32_
   if (!rng || !rng->seed || !out || num_masks < 1 || N < 0 || width < 4 || (width & 3)) return CGVP_ERR_BAD_ARG;
   if (int rc = check_rng(rng)) return rc;
   if (N == 0) return 0;
-  MaskArgs a{rng_args(rng, 0), num_masks, N, width, out};
+  MaskArgs a{rng_args(rng), num_masks, N, width, out};
   const int64_t total = (int64_t)num_masks * N * (width / 4);
   launch<dropout_masks_kernel>(dim3((unsigned)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256)), dim3(256), 0,
                                (hipStream_t)stream, a);
@@ -1256,14 +891,12 @@ int cgvp_gine_conv_bwd(const float* x, const int64_t* ntypes, int32_t num_ntypes
   if (N == 0) return 0;
   if (!x || !g_out || !rowptr || (num_ntypes > 0 && !ntypes)) return CGVP_ERR_BAD_ARG;
   if (E > 0 && (!eperm || !esrc || !edst || (edge_dim > 0 && !eattr) || (num_etypes > 0 && !etypes))) return CGVP_ERR_BAD_ARG;
-  if (((uintptr_t)g_out & 15) || ((uintptr_t)mask & 15)) return CGVP_ERR_BAD_ARG;
+  if (misaligned16({g_out, mask})) return CGVP_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
-  if (g_x) {
-    zero_words(g_x, (size_t)N * (cin - num_ntypes), st);
-  }
+  if (g_x) quad::zero_words(g_x, (size_t)N * (cin - num_ntypes), st);
   int rows = 0, row_len = 0;
   if (int rc = quad::gine_bwd(cin, chid, cout, num_ntypes, num_etypes, edge_dim, x, ntypes, eattr, etypes, rowptr, eperm,
-                              esrc, edst, N, w, act_slope, mask, rng_args(rng, 0), g_out, g_x, workspace, max_workgroups, &rows, &row_len, st)) return rc;
+                              esrc, edst, N, w, act_slope, mask, rng_args(rng), g_out, g_x, workspace, max_workgroups, &rows, &row_len, st)) return rc;
   quad::reduce_slab(workspace, rows, row_len, 0, row_len, grad_layer, st);
   return launch_status();
 }

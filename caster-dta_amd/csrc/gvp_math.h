@@ -1,4 +1,4 @@
-// Per-item GVP arithmetic shared by every kernel in gvp_kernels.hip.
+// Per-item GVP arithmetic of the one-item-per-lane kernels (gvp_kernels.hip), and the arena layout every unit reads.
 //
 // One "item" is one residue or one residue-residue edge; a GPU lane owns one
 // item and keeps all of its channels in registers (every loop below has

@@ -187,6 +187,7 @@ __global__ __launch_bounds__(TPB) void pass_begin_kernel(PassBeginArgs a) {
   typedef Image<NTN, NTE> IM;
   __shared__ __attribute__((aligned(16))) float lds[IM::EMB_SIZE];
   const int b = blockIdx.x;
+  // (csr_count_kernel of graph_index_kernels.hip carries the other copy of this edge test and count: keep the two alike)
   if (b >= a.embed_blocks + a.prep_blocks) {                       // CSR count (malformed edges are dropped, never fault)
     const int64_t e = (int64_t)(b - a.embed_blocks - a.prep_blocks) * TPB + threadIdx.x;
     if (e < a.E) {

@@ -1,4 +1,4 @@
-"""The CSR build, the source-order index and the collate kernel of csrc/gvp_kernels.hip at the sizes their code branches
+"""The CSR build, the source-order index and the collate kernel of csrc/graph_index_kernels.hip at the sizes their code branches
 on: cgvp_csr_from_coo (count, one of two scans, fill, rank), cgvp_src_index (count, scan, fill, rank over sources) and
 cgvp_csr_collate.  All of it is integer arithmetic: the references below are exact and every comparison is array_equal.
 

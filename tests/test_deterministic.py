@@ -71,7 +71,7 @@ def test_isa_of_the_deterministic_kernels_has_no_float_atomics():
     # control: the default instantiation still adds d h[src] with float atomics -- the grep reads the right code
     default = _one(bwd, "conv_bwd2_kernelILi0EfLi1ELi8ELb0E")
     assert any("global_atomic_add_f32" in l for l in default)
-    src = _kernels("gvp_kernels")
+    src = _kernels("graph_index_kernels")
     for name in ("src_count_kernel", "src_fill_kernel", "src_rank_kernel"):
         assert _clean(_one(src, name)), name
 
