@@ -350,7 +350,8 @@ def test_large_batch_linearity(protein_params):
     multi-tile loops of the backward kernels (> 4096 waves' worth of tiles) and the
     private read-add-store accumulation.  Graphs are independent, so the output of
     the big batch equals the outputs of its halves and every weight gradient equals
-    the SUM of the halves' gradients."""
+    the SUM of the halves' gradients.  (The halves run the same multi-tile loops, so this compares the kernels with
+    themselves; test_persistent_loops.py checks those loops against the CPU oracle, at small shapes on shrunken grids.)"""
     model = _encoder(protein_params).eval()
     halves = [ds.protein_batch(120, 31), ds.protein_batch(120, 32)]
     big = ds.collate([dict(x_s=h.x_s[h.ptr[i]:h.ptr[i + 1]], x_v=h.x_v[h.ptr[i]:h.ptr[i + 1]],
