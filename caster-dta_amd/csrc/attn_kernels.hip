@@ -23,7 +23,9 @@
 
 #include <type_traits>
 
+#include "../../include/caster_gvp_attndrop.h"
 #include "gvp_host.h"
+#include "gvp_rng.h"
 
 namespace {
 
@@ -94,8 +96,33 @@ __device__ __forceinline__ bool locate(const int64_t* __restrict__ ptr, int B, i
 __device__ __forceinline__ Prob pick(const Args& a, int pi) { return pi ? a.p[1] : a.p[0]; }
 __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 
+// ------------------------------------------------------------------------------------------------ attention dropout
+// nn.MultiheadAttention's training arithmetic (include/caster_gvp_attndrop.h): the PROBABILITIES are dropped, after the
+// softmax and before the product with V.  The three kernels are templates on DROP; a DROP = true instantiation takes the
+// per-problem generator arguments as a second kernel argument and multiplies the score tile, where it sits in registers,
+// by factors f[q][k] in {0, 1/(1-p)} regenerated from (seed, offset, stream, head, q, k) (gvp_rng.h) -- nothing is
+// stored.  The softmax normaliser and the saved log-sum-exp stay those of the undropped scores.
+struct Drop { const unsigned long long* seed[2]; gvp::DropRule rule[2]; int stream[2]; };
+struct NoDrop { int unused; };
+template <bool DROP> using DropOf = std::conditional_t<DROP, Drop, NoDrop>;
+
+// What a wave needs of its problem's generator.  `on` is wave-uniform: a problem with p = 0 beside one with p > 0 skips
+// the generator and keeps factor 1.
+struct Site { unsigned long long seed, offset; gvp::DropRule rule; int stream; bool on; };
+__device__ __forceinline__ Site site_of(const Drop& d, int pi) {
+  Site s;
+  const unsigned long long* sp = pi ? d.seed[1] : d.seed[0];
+  s.rule = pi ? d.rule[1] : d.rule[0];
+  s.stream = pi ? d.stream[1] : d.stream[0];
+  s.on = sp != nullptr && s.rule.thr < 65536u;
+  s.seed = s.on ? sp[0] : 0ull;
+  s.offset = s.on ? sp[1] : 0ull;
+  return s;
+}
+
 // ------------------------------------------------------------------------------------------------ forward
-__global__ __launch_bounds__(TPB) void attn_fwd_kernel(Args a) {
+template <bool DROP>
+__global__ __launch_bounds__(TPB) void attn_fwd_kernel(Args a, DropOf<DROP> d) {
   const int lane = threadIdx.x & 63, n = lane & 15, g = lane >> 4;
   int64_t u = (int64_t)blockIdx.x * WPB + wave_id();
   int pi = 0;
@@ -148,6 +175,10 @@ __global__ __launch_bounds__(TPB) void attn_fwd_kernel(Args a) {
   f4 kk_n = {0.f, 0.f, 0.f, 0.f};
   float va_n[4] = {0.f, 0.f, 0.f, 0.f};
   if (k0 < k_end) load_tile(kk_n, va_n);
+  // DROP: this lane's 1 x 4 key run starts at key kb + 4g = 4 (kblk0 + g) + sk, sk the same for the whole pair
+  [[maybe_unused]] Site S;
+  [[maybe_unused]] unsigned sk = 0;
+  if constexpr (DROP) { S = site_of(d, pi); sk = (unsigned)__builtin_amdgcn_readfirstlane(k0 & 3); }
   auto tile = [&](int kb, auto tail) {
     const f4 kk = kk_n;
     const float va[4] = {va_n[0], va_n[1], va_n[2], va_n[3]};
@@ -168,6 +199,14 @@ __global__ __launch_bounds__(TPB) void attn_fwd_kernel(Args a) {
     l = l * alpha + quad_sum(ps);
     acc *= alpha;
     m = m_new;
+    if constexpr (DROP) {                                   // after the row sum: l and the lse are the undropped ones
+      if (S.on) {
+        float f[4];
+        gvp::attn_drop_run_k(S.seed, S.offset, S.stream, h, (unsigned)qr, ((unsigned)(kb - (int)sk) >> 2) + g, sk, S.rule, f);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) p[r] *= f[r];           // (a key past the pair's end has p = 0 and stays 0)
+      }
+    }
 #pragma unroll
     for (int r = 0; r < 4; ++r) acc = mfma(va[r], p[r], acc);
   };
@@ -183,7 +222,8 @@ __global__ __launch_bounds__(TPB) void attn_fwd_kernel(Args a) {
 
 // ------------------------------------------------------------------------------------------------ backward: d Q
 // Same orientation as the forward.  Also writes delta[q][h] = sum_d dO[q][d] O[q][d] for the d K / d V kernel.
-__global__ __launch_bounds__(TPB) void attn_bwd_dq_kernel(Args a) {
+template <bool DROP>
+__global__ __launch_bounds__(TPB) void attn_bwd_dq_kernel(Args a, DropOf<DROP> d) {
   const int lane = threadIdx.x & 63, n = lane & 15, g = lane >> 4;
   int64_t u = (int64_t)blockIdx.x * WPB + wave_id();
   int pi = 0;
@@ -235,6 +275,9 @@ __global__ __launch_bounds__(TPB) void attn_bwd_dq_kernel(Args a) {
   f4 kk_n = {0.f, 0.f, 0.f, 0.f}, vv_n = {0.f, 0.f, 0.f, 0.f};
   float ka_n[4] = {0.f, 0.f, 0.f, 0.f};
   if (k0 < k_end) load_tile(kk_n, vv_n, ka_n);
+  [[maybe_unused]] Site S;                                          // DROP: the forward's factors again, see attn_fwd_kernel
+  [[maybe_unused]] unsigned sk = 0;
+  if constexpr (DROP) { S = site_of(d, pi); sk = (unsigned)__builtin_amdgcn_readfirstlane(k0 & 3); }
   auto tile = [&](int kb, auto tail) {
     const f4 kk = kk_n, vv = vv_n;
     const float ka[4] = {ka_n[0], ka_n[1], ka_n[2], ka_n[3]};
@@ -242,6 +285,14 @@ __global__ __launch_bounds__(TPB) void attn_bwd_dq_kernel(Args a) {
     f4 st = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int s = 0; s < 4; ++s) { st = mfma(kk[s], qs[s], st); dp = mfma(vv[s], go[s], dp); }
+    if constexpr (DROP) {                                           // d P = (d O V^T) o f
+      if (S.on) {
+        float f[4];
+        gvp::attn_drop_run_k(S.seed, S.offset, S.stream, h, (unsigned)qr, ((unsigned)(kb - (int)sk) >> 2) + g, sk, S.rule, f);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dp[r] *= f[r];
+      }
+    }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       // (a lane without a query computes a finite column that is never stored; keys past the pair's end only in the tail)
@@ -262,7 +313,8 @@ __global__ __launch_bounds__(TPB) void attn_bwd_dq_kernel(Args a) {
 //   dP[q][key]  = D[m = q][n = key]: A = dO rows, B = V rows
 //   dV[key][d]  = D[m = d][n = key] += sum_q dO[q][d] P[q][key]   A: lane (m = d, g), slot r <-> query qb + 4g + r
 //   dK[key][d]  = D[m = d][n = key] += sum_q Qs[q][d] dS[q][key]
-__global__ __launch_bounds__(TPB) void attn_bwd_dkv_kernel(Args a) {
+template <bool DROP>
+__global__ __launch_bounds__(TPB) void attn_bwd_dkv_kernel(Args a, DropOf<DROP> d) {
   const int lane = threadIdx.x & 63, n = lane & 15, g = lane >> 4;
   int64_t u = (int64_t)blockIdx.x * WPB + wave_id();
   int pi = 0;
@@ -311,6 +363,11 @@ __global__ __launch_bounds__(TPB) void attn_bwd_dkv_kernel(Args a) {
   };
   QT nxt = {};
   if (q0 < q_end) load_tile(nxt);
+  // DROP: this lane's 4 x 1 query run starts at query qb + 4g = 2 (h0 + 2g) + sq, sq the same for the whole pair; the
+  // factors are those the forward applied to (query, key kr)
+  [[maybe_unused]] Site S;
+  [[maybe_unused]] unsigned sq = 0;
+  if constexpr (DROP) { S = site_of(d, pi); sq = (unsigned)__builtin_amdgcn_readfirstlane(q0 & 1); }
   auto tile = [&](int qb, auto tail) {
     const QT cur = nxt;
     load_tile(nxt);
@@ -319,13 +376,23 @@ __global__ __launch_bounds__(TPB) void attn_bwd_dkv_kernel(Args a) {
     f4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int x = 0; x < 4; ++x) { s = mfma(qa[x], kk[x], s); dp = mfma(ga[x], vv[x], dp); }
+    [[maybe_unused]] float f[4] = {1.f, 1.f, 1.f, 1.f};
+    if constexpr (DROP) {
+      if (S.on)
+        gvp::attn_drop_run_q(S.seed, S.offset, S.stream, h, ((unsigned)(qb - (int)sq) >> 1) + 2 * g, sq, (unsigned)kr, S.rule, f);
+    }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       // (a lane without a key computes a finite column that is never stored; queries past the pair's end only in the tail)
       float pr = fexp(s[r] - lse[r]);
       if constexpr (decltype(tail)::value) pr = qb + 4 * g + r < q_end ? pr : 0.f;
-      accv = mfma(gt[r], pr, accv);
-      acck = mfma(qt[r], pr * (dp[r] - dl[r]), acck);
+      if constexpr (DROP) {                                 // d V = (P o f)^T d O,  d S = P o (d P o f - delta)
+        accv = mfma(gt[r], pr * f[r], accv);
+        acck = mfma(qt[r], pr * (dp[r] * f[r] - dl[r]), acck);
+      } else {
+        accv = mfma(gt[r], pr, accv);
+        acck = mfma(qt[r], pr * (dp[r] - dl[r]), acck);
+      }
     }
   };
   int qb = q0;
@@ -388,11 +455,12 @@ __global__ __launch_bounds__(TPB) void attn_weights_kernel(Args a) {
 // keys, the forward and d Q kernels; 2: over the queries, the d K / d V kernel).  Workgroups start in index order: with
 // the residues -> atoms direction first, its 10k three-tile waves filled the chip and the 1.8k nineteen-tile waves of the
 // other direction started last and ran alone at the end of the launch.
-int fill(Args& a, const cgvp_attn_problem* probs, int nprob, int64_t B, int H, int long_first = 0) {
+int fill(Args& a, const cgvp_attn_problem* probs, int nprob, int64_t B, int H, int long_first = 0, bool* swapped = nullptr) {
   if (!probs || nprob < 1 || nprob > 2 || B < 0 || H < 1) return CGVP_ERR_BAD_ARG;
   a.nprob = nprob; a.B = (int)B; a.H = H; a.E = H * HD;
   const bool swap = nprob == 2 && ((long_first == 1 && probs[1].num_k > probs[0].num_k) ||
                                    (long_first == 2 && probs[1].num_q > probs[0].num_q));
+  if (swapped) *swapped = swap;
   for (int i = 0; i < 2; ++i) {
     Prob& p = a.p[i];
     p = Prob{};
@@ -414,19 +482,81 @@ int fill(Args& a, const cgvp_attn_problem* probs, int nprob, int64_t B, int H, i
   return 0;
 }
 
+// The generator arguments of a call: 0 = no dropout anywhere (the DROP = false kernels run), 1 = at least one problem
+// drops, < 0 = CGVP_ERR_BAD_ARG.  `nprob` has passed fill().
+int drop_of(Drop& d, const cgvp_rng* rng, int nprob, int H) {
+  d = Drop{};
+  d.rule[0] = d.rule[1] = gvp::drop_rule(0.f);
+  if (H > gvp::kAttnDropMaxHeads) return CGVP_ERR_BAD_ARG;      // the head has 7 bits of the counter
+  int any = 0;
+  for (int i = 0; rng && i < nprob; ++i) {
+    const cgvp_rng& r = rng[i];
+    if (!(r.p >= 0.f && r.p < 1.f) || ((uintptr_t)r.seed & 7)) return CGVP_ERR_BAD_ARG;       // (a NaN fails the first)
+    if (!r.seed) continue;
+    d.seed[i] = reinterpret_cast<const unsigned long long*>(r.seed);
+    d.rule[i] = gvp::drop_rule(r.p);
+    d.stream[i] = r.stream;
+    any |= d.rule[i].thr < 65536u;
+  }
+  return any;
+}
+Drop ordered(const Drop& d, bool swap) {                          // in the order fill() gave the problems
+  if (!swap) return d;
+  return Drop{{d.seed[1], d.seed[0]}, {d.rule[1], d.rule[0]}, {d.stream[1], d.stream[0]}};
+}
+
+int attn_fwd(const cgvp_attn_problem* probs, int nprob, int64_t B, int H, float scale, const cgvp_rng* rng, bool check_rng,
+             hipStream_t st) {
+  Args a;
+  bool swap = false;
+  if (int rc = fill(a, probs, nprob, B, H, 1, &swap)) return rc;
+  a.scale = scale;
+  Drop d;
+  const int drop = check_rng ? drop_of(d, rng, nprob, H) : 0;
+  if (drop < 0) return drop;
+  if (B == 0) return 0;
+  const int64_t units = ((int64_t)a.p[0].units_q + a.p[1].units_q) * H;
+  const dim3 grid((unsigned)((units + WPB - 1) / WPB));
+  if (drop) launch<attn_fwd_kernel<true>>(grid, dim3(TPB), 0, st, a, ordered(d, swap));
+  else launch<attn_fwd_kernel<false>>(grid, dim3(TPB), 0, st, a, NoDrop{});
+  return launch_status();
+}
+
+int attn_bwd(const cgvp_attn_problem* probs, int nprob, int64_t B, int H, float scale, const cgvp_rng* rng, bool check_rng,
+             hipStream_t st) {
+  Args a, ak;
+  bool swap = false, swap_k = false;
+  if (int rc = fill(a, probs, nprob, B, H, 1, &swap)) return rc;
+  if (int rc = fill(ak, probs, nprob, B, H, 2, &swap_k)) return rc;
+  a.scale = ak.scale = scale;
+  for (int i = 0; i < nprob; ++i) {
+    const cgvp_attn_problem& s = probs[i];
+    if ((s.num_q > 0 && (!s.g_out || !s.g_q || !s.delta)) || (s.num_k > 0 && (!s.g_k || !s.g_v))) return CGVP_ERR_BAD_ARG;
+  }
+  Drop d;
+  const int drop = check_rng ? drop_of(d, rng, nprob, H) : 0;
+  if (drop < 0) return drop;
+  if (B == 0) return 0;
+  const int64_t uq = ((int64_t)a.p[0].units_q + a.p[1].units_q) * H;
+  const int64_t uk = ((int64_t)a.p[0].units_k + a.p[1].units_k) * H;
+  const dim3 gq((unsigned)((uq + WPB - 1) / WPB)), gk((unsigned)((uk + WPB - 1) / WPB));
+  if (drop) {
+    launch<attn_bwd_dq_kernel<true>>(gq, dim3(TPB), 0, st, a, ordered(d, swap));
+    launch<attn_bwd_dkv_kernel<true>>(gk, dim3(TPB), 0, st, ak, ordered(d, swap_k));
+  } else {
+    launch<attn_bwd_dq_kernel<false>>(gq, dim3(TPB), 0, st, a, NoDrop{});
+    launch<attn_bwd_dkv_kernel<false>>(gk, dim3(TPB), 0, st, ak, NoDrop{});
+  }
+  return launch_status();
+}
+
 }  // namespace
 
 extern "C" {
 
 int cgvp_attn_fwd(const cgvp_attn_problem* probs, int32_t num_problems, int64_t num_pairs, int32_t heads, float scale,
                   void* stream) {
-  Args a;
-  if (int rc = fill(a, probs, num_problems, num_pairs, heads, 1)) return rc;
-  a.scale = scale;
-  if (num_pairs == 0) return 0;
-  const int64_t units = ((int64_t)a.p[0].units_q + a.p[1].units_q) * heads;
-  launch<attn_fwd_kernel>(dim3((unsigned)((units + WPB - 1) / WPB)), dim3(TPB), 0, (hipStream_t)stream, a);
-  return launch_status();
+  return attn_fwd(probs, num_problems, num_pairs, heads, scale, nullptr, false, (hipStream_t)stream);
 }
 
 int cgvp_attn_weights(const cgvp_attn_problem* probs, int32_t num_problems, int64_t num_pairs, int32_t heads, float scale,
@@ -444,20 +574,20 @@ int cgvp_attn_weights(const cgvp_attn_problem* probs, int32_t num_problems, int6
 
 int cgvp_attn_bwd(const cgvp_attn_problem* probs, int32_t num_problems, int64_t num_pairs, int32_t heads, float scale,
                   void* stream) {
-  Args a, ak;
-  if (int rc = fill(a, probs, num_problems, num_pairs, heads, 1)) return rc;
-  if (int rc = fill(ak, probs, num_problems, num_pairs, heads, 2)) return rc;
-  a.scale = ak.scale = scale;
-  for (int i = 0; i < num_problems; ++i) {
-    const cgvp_attn_problem& s = probs[i];
-    if ((s.num_q > 0 && (!s.g_out || !s.g_q || !s.delta)) || (s.num_k > 0 && (!s.g_k || !s.g_v))) return CGVP_ERR_BAD_ARG;
-  }
-  if (num_pairs == 0) return 0;
-  const int64_t uq = ((int64_t)a.p[0].units_q + a.p[1].units_q) * heads;
-  const int64_t uk = ((int64_t)a.p[0].units_k + a.p[1].units_k) * heads;
-  launch<attn_bwd_dq_kernel>(dim3((unsigned)((uq + WPB - 1) / WPB)), dim3(TPB), 0, (hipStream_t)stream, a);
-  launch<attn_bwd_dkv_kernel>(dim3((unsigned)((uk + WPB - 1) / WPB)), dim3(TPB), 0, (hipStream_t)stream, ak);
-  return launch_status();
+  return attn_bwd(probs, num_problems, num_pairs, heads, scale, nullptr, false, (hipStream_t)stream);
+}
+
+// ---- include/caster_gvp_attndrop.h
+int cgvp_attn_dropout_version(void) { return CGVP_ATTN_DROPOUT_VERSION; }
+
+int cgvp_attn_fwd_dropout(const cgvp_attn_problem* probs, int32_t num_problems, int64_t num_pairs, int32_t heads, float scale,
+                          const cgvp_rng* rng, void* stream) {
+  return attn_fwd(probs, num_problems, num_pairs, heads, scale, rng, true, (hipStream_t)stream);
+}
+
+int cgvp_attn_bwd_dropout(const cgvp_attn_problem* probs, int32_t num_problems, int64_t num_pairs, int32_t heads, float scale,
+                          const cgvp_rng* rng, void* stream) {
+  return attn_bwd(probs, num_problems, num_pairs, heads, scale, rng, true, (hipStream_t)stream);
 }
 
 }  // extern "C"

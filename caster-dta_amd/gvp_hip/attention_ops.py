@@ -15,6 +15,7 @@ reference's dense [B, Lq_max, Lk_max] layout for inference (inference/evaluation
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 from typing import Tuple
 
@@ -132,6 +133,129 @@ def _attn_backward(ctx, g_o_r, g_o_a, g_lse_r, g_lse_a):
 
 torch.library.register_autograd("caster_gvp::cross_attention", _attn_backward, setup_context=_attn_setup)
 torch.library.register_autocast("caster_gvp::cross_attention", "cuda", torch.float32)
+
+
+# ------------------------------------------------------------------------------------------------ attention dropout
+# include/caster_gvp_attndrop.h: the same kernels with nn.MultiheadAttention's training-mode dropout on the softmax
+# probabilities, factors regenerated in the kernels from the step's {seed, offset} pair -- a header, a version and a
+# signature table of their own, bound on the handle of `_lib.lib()`.
+ATTN_DROPOUT_VERSION = 1     # CGVP_ATTN_DROPOUT_VERSION
+DROPOUT_MAX_HEADS = 128      # CGVP_ATTN_DROPOUT_MAX_HEADS
+
+_DROP_ARGS = [C.POINTER(_lib.AttnProblem), C.c_int32, C.c_int64, C.c_int32, C.c_float, C.POINTER(_lib.Rng), C.c_void_p]
+_DROP_SIGNATURES = {
+    "cgvp_attn_dropout_version": (C.c_int, []),
+    "cgvp_attn_fwd_dropout": (C.c_int, _DROP_ARGS),
+    "cgvp_attn_bwd_dropout": (C.c_int, _DROP_ARGS),
+}
+
+
+def dropout_exported_symbols():
+    """Names include/caster_gvp_attndrop.h declares."""
+    return tuple(_DROP_SIGNATURES)
+
+
+@functools.lru_cache(maxsize=None)
+def dropout_lib():
+    """libcaster_gvp.so (the handle of `_lib.lib()`) with the attention-dropout entry points typed (once)."""
+    return _lib.bind(_lib.lib(), _DROP_SIGNATURES, "cgvp_attn_dropout_version", ATTN_DROPOUT_VERSION,
+                     "attention-dropout version")
+
+
+def _rngs(pair, site_r, site_a, p_r, p_a):
+    if pair.dtype != torch.int64 or pair.numel() != 2 or not pair.is_cuda or not pair.is_contiguous():
+        raise ValueError("pair must be the int64[2] {seed, offset} of caster_gvp::rng_next on the GPU")
+    R = (_lib.Rng * 2)()
+    for r, site, p in zip(R, (site_r, site_a), (p_r, p_a)):
+        r.seed, r.p, r.stream = pair.data_ptr(), float(p), int(site)
+    return R
+
+
+@torch.library.custom_op("caster_gvp::cross_attention_dropout", mutates_args=(), device_types="cuda")
+def cross_attention_dropout_op(q_r: Tensor, k_a: Tensor, v_a: Tensor, q_a: Tensor, k_r: Tensor, v_r: Tensor, rptr: Tensor,
+                               aptr: Tensor, heads: int, pair: Tensor, site_r: int, site_a: int, p_r: float,
+                               p_a: float) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """`cross_attention` with dropout on the softmax probabilities (nn.MultiheadAttention in training mode):
+    o = (softmax(q k^T / 4) o f) v, f in {0, 1/(1-p)} a pure function of (pair, site, head, query row, key row).
+    -> (o_r, o_a, lse_r, lse_a); the lse are those of the UNdropped scores.  p_r = p_a = 0 is `cross_attention`."""
+    _check(q_r, k_a, v_a, q_a, k_r, v_r, rptr, aptr, heads)
+    ts = [_f32(t, "attention operand") for t in (q_r, k_a, v_a, q_a, k_r, v_r)]
+    rptr, aptr = _i64c(rptr, "rptr"), _i64c(aptr, "aptr")
+    dev = ts[0].device
+    N, Na, B = int(q_r.shape[0]), int(q_a.shape[0]), int(rptr.numel()) - 1
+    f32 = dict(dtype=torch.float32, device=dev)
+    o_r, o_a = torch.empty(N, heads * HEAD_DIM, **f32), torch.empty(Na, heads * HEAD_DIM, **f32)
+    lse_r, lse_a = torch.empty(N, heads, **f32), torch.empty(Na, heads, **f32)
+    P = _problems(*ts, rptr, aptr)
+    P[0].out, P[0].lse, P[1].out, P[1].lse = _ptr(o_r).value or 0, _ptr(lse_r).value or 0, _ptr(o_a).value or 0, _ptr(lse_a).value or 0
+    R = _rngs(pair, site_r, site_a, p_r, p_a)
+    with torch.cuda.device(dev):
+        _lib.check(dropout_lib().cgvp_attn_fwd_dropout(P, 2, B, heads, 1.0 / math.sqrt(HEAD_DIM), R, _stream()),
+                   "cgvp_attn_fwd_dropout")
+    return o_r, o_a, lse_r, lse_a
+
+
+@cross_attention_dropout_op.register_fake
+def _(q_r, k_a, v_a, q_a, k_r, v_r, rptr, aptr, heads, pair, site_r, site_a, p_r, p_a):
+    f = lambda t, *s: t.new_empty(s, dtype=torch.float32)
+    return (f(q_r, q_r.shape[0], q_r.shape[1]), f(q_a, q_a.shape[0], q_a.shape[1]), f(q_r, q_r.shape[0], heads),
+            f(q_a, q_a.shape[0], heads))
+
+
+@torch.library.custom_op("caster_gvp::cross_attention_dropout_backward", mutates_args=(), device_types="cuda")
+def cross_attention_dropout_backward_op(g_o_r: Tensor, g_o_a: Tensor, q_r: Tensor, k_a: Tensor, v_a: Tensor, q_a: Tensor,
+                                        k_r: Tensor, v_r: Tensor, o_r: Tensor, o_a: Tensor, lse_r: Tensor, lse_a: Tensor,
+                                        rptr: Tensor, aptr: Tensor, heads: int, pair: Tensor, site_r: int, site_a: int,
+                                        p_r: float, p_a: float) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """-> (g_q_r, g_k_a, g_v_a, g_q_a, g_k_r, g_v_r); `pair`, sites and p are the forward's: the factors are regenerated."""
+    ts = [_f32(t, "attention operand") for t in (q_r, k_a, v_a, q_a, k_r, v_r)]
+    g_o_r, g_o_a, o_r, o_a = (_f32(t, "attention gradient") for t in (g_o_r, g_o_a, o_r, o_a))
+    lse_r, lse_a = _f32(lse_r, "lse"), _f32(lse_a, "lse")
+    rptr, aptr = _i64c(rptr, "rptr"), _i64c(aptr, "aptr")
+    dev = ts[0].device
+    B = int(rptr.numel()) - 1
+    outs = [torch.empty_like(t) for t in ts]                 # g_q_r, g_k_a, g_v_a, g_q_a, g_k_r, g_v_r
+    d_r, d_a = torch.empty_like(lse_r), torch.empty_like(lse_a)
+    P = _problems(*ts, rptr, aptr)
+    v = lambda t: _ptr(t).value or 0
+    P[0].out, P[0].lse, P[0].g_out, P[0].delta = v(o_r), v(lse_r), v(g_o_r), v(d_r)
+    P[0].g_q, P[0].g_k, P[0].g_v = v(outs[0]), v(outs[1]), v(outs[2])
+    P[1].out, P[1].lse, P[1].g_out, P[1].delta = v(o_a), v(lse_a), v(g_o_a), v(d_a)
+    P[1].g_q, P[1].g_k, P[1].g_v = v(outs[3]), v(outs[4]), v(outs[5])
+    R = _rngs(pair, site_r, site_a, p_r, p_a)
+    with torch.cuda.device(dev):
+        _lib.check(dropout_lib().cgvp_attn_bwd_dropout(P, 2, B, heads, 1.0 / math.sqrt(HEAD_DIM), R, _stream()),
+                   "cgvp_attn_bwd_dropout")
+    return tuple(outs)
+
+
+@cross_attention_dropout_backward_op.register_fake
+def _(g_o_r, g_o_a, q_r, k_a, v_a, q_a, k_r, v_r, o_r, o_a, lse_r, lse_a, rptr, aptr, heads, pair, site_r, site_a, p_r, p_a):
+    return tuple(t.new_empty(t.shape, dtype=torch.float32) for t in (q_r, k_a, v_a, q_a, k_r, v_r))
+
+
+def _drop_setup(ctx, inputs, output):
+    q_r, k_a, v_a, q_a, k_r, v_r, rptr, aptr, heads, pair, site_r, site_a, p_r, p_a = inputs
+    o_r, o_a, lse_r, lse_a = output
+    ctx.heads, ctx.sites, ctx.ps = heads, (site_r, site_a), (p_r, p_a)
+    ctx.set_materialize_grads(False)          # the log-sum-exp outputs never carry a gradient, as in _attn_setup
+    ctx.save_for_backward(q_r, k_a, v_a, q_a, k_r, v_r, o_r, o_a, lse_r, lse_a, rptr, aptr, pair)
+
+
+def _drop_backward(ctx, g_o_r, g_o_a, g_lse_r, g_lse_a):
+    q_r, k_a, v_a, q_a, k_r, v_r, o_r, o_a, lse_r, lse_a, rptr, aptr, pair = ctx.saved_tensors
+    if g_o_r is None and g_o_a is None:
+        return (None,) * 14
+    g_o_r = torch.zeros_like(o_r) if g_o_r is None else g_o_r
+    g_o_a = torch.zeros_like(o_a) if g_o_a is None else g_o_a
+    grads = torch.ops.caster_gvp.cross_attention_dropout_backward(
+        g_o_r.contiguous(), g_o_a.contiguous(), q_r, k_a, v_a, q_a, k_r, v_r, o_r, o_a, lse_r, lse_a, rptr, aptr, ctx.heads,
+        pair, *ctx.sites, *ctx.ps)
+    return (*grads, *(None,) * 8)
+
+
+torch.library.register_autograd("caster_gvp::cross_attention_dropout", _drop_backward, setup_context=_drop_setup)
+torch.library.register_autocast("caster_gvp::cross_attention_dropout", "cuda", torch.float32)
 
 
 @torch.library.custom_op("caster_gvp::cross_attention_weights", mutates_args=(), device_types="cuda")

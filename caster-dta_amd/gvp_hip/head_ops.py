@@ -202,6 +202,12 @@ def _(state):
     return state.new_empty((2,))
 
 
+def own_pair(device):
+    """One generator advance for a caller outside an active `DropSites` (attention dropout under autocast or
+    torch.compile, or without dropout in the rest of the head): a fresh {seed, offset} pair of the head's state."""
+    return torch.ops.caster_gvp.rng_next(_head_rng_state(device))
+
+
 def _rng(pair, p, site):
     return C.byref(Rng(pair.data_ptr(), float(p), int(site))) if p > 0 else None
 

@@ -12,7 +12,8 @@ by `batch`, then the affinity MLP.  With `ptr` offsets in the input dicts (what
 `forward_with_graphs` passes) the step has no data-dependent shape and no host
 synchronisation, so it captures into a HIP graph.  The reference's dense
 formulation (`to_dense_batch` + nn.MultiheadAttention) is kept for head shapes the
-kernel is not compiled for (head_dim != 16, attention dropout > 0).
+kernel is not compiled for (head_dim != 16); attention dropout is drawn inside
+the kernel (`caster_gvp::cross_attention_dropout`).
 It does not import torch_geometric (`to_dense_batch` is restated below).
 
 Multi-GPU: independent protein/drug pairs shard across ranks (one process per
@@ -527,10 +528,11 @@ class CrossAttentionModule(nn.Module):
 
     # ------------------------------------------------------------ varlen path (MI355X kernel)
     def varlen_supported(self, rows):
-        """The varlen kernel is compiled for head_dim 16 without attention dropout, on CUDA fp32 rows."""
+        """The varlen kernel is compiled for head_dim 16 on CUDA rows; attention dropout in training mode is drawn inside
+        it (caster_gvp::cross_attention_dropout)."""
         m1, m2 = self.embed1_to_2, self.embed2_to_1
         return (rows.is_cuda and m1.head_dim == 16 and m2.head_dim == 16 and m1.embed_dim == m2.embed_dim
-                and m1.num_heads == m2.num_heads and not (self.training and (m1.dropout > 0 or m2.dropout > 0)))
+                and m1.num_heads == m2.num_heads)
 
     @staticmethod
     def _proj_parts(mha):
@@ -570,7 +572,12 @@ class CrossAttentionModule(nn.Module):
         graph b of side 1 attends to graph b of side 2 and vice versa (joint_gnn.py:376-398).  The softmax(QK^T)V
         core of both directions is one launch of caster_gvp::cross_attention; projections and feed-forward are
         GEMMs on the compact rows.  Returns (embed_1, embed_2, (w1, w2) or None).  `scores_out`: a list this layer
-        appends its NodeAttention to (caster_gvp::cross_attention_node_scores: one launch, no host read)."""
+        appends its NodeAttention to (caster_gvp::cross_attention_node_scores: one launch, no host read).
+
+        In training mode with attention dropout > 0 the core is caster_gvp::cross_attention_dropout: the probabilities
+        are dropped inside the kernels, from `sites.pair` when the row-wise sites are active and from a pair of this
+        layer's own otherwise.  The weights and node scores returned then are the UNDROPPED probabilities
+        (nn.MultiheadAttention returns the dropped ones); the defaults produce them in eval mode only."""
         from gvp_hip import attention_ops  # noqa: F401  (registers the ops)
         from gvp_hip.head_ops import fast_layer_norm      # nn.LayerNorm on compact rows: one-pass kernels each way
         if lanes is None:
@@ -590,7 +597,16 @@ class CrossAttentionModule(nn.Module):
         heads = self.embed1_to_2.num_heads
         from gvp_hip import head_ops
         br = head_ops._bridge()
-        if br is not None and hasattr(br, "head_cross_attention") and not torch.is_autocast_enabled("cuda"):
+        p1, p2 = float(self.embed1_to_2.dropout), float(self.embed2_to_1.dropout)
+        if self.training and (p1 > 0 or p2 > 0):
+            # attention dropout inside the kernels: the step's pair when the row-wise sites are active, else one of this
+            # layer's own (autocast, torch.compile, no dropout in the rest of the head); two fresh site ids either way
+            if sites is None:
+                sites = head_ops.DropSites(embed_1, False, 0.0)
+            pair = sites.pair if sites.active else head_ops.own_pair(embed_1.device)
+            o1, o2, lse1, lse2 = torch.ops.caster_gvp.cross_attention_dropout(
+                q1, k1, v1, q2, k2, v2, ptr1, ptr2, heads, pair, sites._next(), sites._next(), p1, p2)
+        elif br is not None and hasattr(br, "head_cross_attention") and not torch.is_autocast_enabled("cuda"):
             o1, o2, lse1, lse2 = br.head_cross_attention(q1, k1, v1, q2, k2, v2, ptr1, ptr2, heads)     # eager: C++ autograd function
         else:
             o1, o2, lse1, lse2 = torch.ops.caster_gvp.cross_attention(q1, k1, v1, q2, k2, v2, ptr1, ptr2, heads)

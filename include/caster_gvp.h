@@ -425,7 +425,8 @@ int cgvp_edge_featurise(const float* ca_xyz, const int64_t* seq_index, const int
  * head_dim is 16 (embed 128 / 8 heads in CASTER-DTA; embed = 16 * heads in general); q / k / v / out are
  * [rows][16 * heads] fp32 row-major (the projected tensors), lse [num_q][heads] is the log-sum-exp the backward
  * needs.  A pair without keys yields zero rows.  One call takes up to TWO problems (the module's two directions run
- * in one launch).  No attention dropout (the reference trains with attention_dropout = 0, train_model.py:317). */
+ * in one launch).  No attention dropout here (the reference trains with attention_dropout = 0, train_model.py:317);
+ * the training-mode variants with dropout on the probabilities are declared in caster_gvp_attndrop.h. */
 typedef struct {
   const float* q; const float* k; const float* v;
   const int64_t* q_ptr; const int64_t* k_ptr;   /* [num_pairs + 1] row offsets                            */
