@@ -19,18 +19,22 @@
 // workgroup take the pair's query tiles round robin (an atom-key tile of a long protein walks hundreds of them); two
 // xor-shuffles join the four lane groups of a wave, LDS joins the waves in wave order.  No atomics: the order of every
 // sum is fixed by the shape alone.
+//
+// head_dim 16 M (include/caster_gvp_attnhd.h): a template on (H, M) for H M <= 8, an embed width of at most 128.  A row
+// is H M chunks of 16 dims, chunk j = h M + c at column 16 j: the loads walk the chunks, a head's score sums its M.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <type_traits>
 
+#include "../../include/caster_gvp_attnhd.h"
 #include "../../include/caster_gvp_attnscore.h"
 #include "gvp_host.h"
 
 namespace {
 
 typedef float f4 __attribute__((ext_vector_type(4)));
-constexpr int WAVE = 64, TILE = 16, HD = 16, WPB = 8, TPB = WAVE * WPB, MAX_H = CGVP_ATTN_SCORE_MAX_HEADS;
+constexpr int WAVE = 64, TILE = 16, WPB = 8, TPB = WAVE * WPB, MAX_H = CGVP_ATTN_SCORE_MAX_HEADS;
 
 __device__ __forceinline__ f4 mfma(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 // exp through v_exp_f32, as in attn_kernels.hip (the lse was produced with the same function)
@@ -90,8 +94,9 @@ __device__ __forceinline__ bool locate(const int64_t* __restrict__ ptr, int B, i
 __device__ __forceinline__ Prob pick(const Args& a, int pi) { return pi ? a.p[1] : a.p[0]; }
 __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 
-template <int H>
+template <int H, int M>
 __global__ __launch_bounds__(TPB) void attn_node_scores_kernel(Args a) {
+  constexpr int J = H * M;                                        // 16-dim chunks of a row: chunk h M + c of head h
   __shared__ float2 part[WPB][TILE];                              // per wave and key: H x {sum, max} of w over the wave's queries
   const int lane = threadIdx.x & 63, n = lane & 15, g = lane >> 4, wv = wave_id();
   int64_t t = blockIdx.x;
@@ -108,22 +113,22 @@ __global__ __launch_bounds__(TPB) void attn_node_scores_kernel(Args a) {
   const int q0 = (int)P.q_ptr[b], q_end = (int)P.q_ptr[b + 1];
   const int kr = kt0 + n;
   const bool kv = kr < k_end;
-  constexpr unsigned E = H * HD;
+  constexpr unsigned E = J * TILE;
   float sum = 0.f, mx = 0.f;                                      // weights are >= 0: 0 is the maximum of no query
   int qb = q0 + TILE * wv;                                        // this wave's first query tile; the stride is WPB tiles
   if (qb < q_end) {
     // K of every head: a lane behind the pair's last key reads that last key's row (the tile holds at least one key)
     // and computes a finite column that is never stored
-    f4 kk[H];
+    f4 kk[J];
     {
       const unsigned ko = (unsigned)(kv ? kr : k_end - 1) * E + 4 * g;
 #pragma unroll
-      for (int h = 0; h < H; ++h) kk[h] = *reinterpret_cast<const f4*>(P.k + ko + h * HD);
+      for (int j = 0; j < J; ++j) kk[j] = *reinterpret_cast<const f4*>(P.k + ko + j * TILE);
     }
     // The next query tile is loaded while the current one is computed, unconditionally, on offsets that advance per
     // call and are clamped to the pair's last query (see attn_fwd_kernel): rows behind q_end are copies of the last
     // query's and are zeroed in the peeled tail iteration only.
-    struct QT { f4 qa[H]; float lse[4][H]; };
+    struct QT { f4 qa[J]; float lse[4][H]; };
     const unsigned q_step = WPB * TILE * E, h_step = WPB * TILE * H;
     const unsigned qo_last = (unsigned)(q_end - 1) * E + 4 * g, ho_last = (unsigned)(q_end - 1) * H;
     unsigned qo = (unsigned)(qb + n) * E + 4 * g;                 // this lane's row as the M index of the score product
@@ -134,7 +139,7 @@ __global__ __launch_bounds__(TPB) void attn_node_scores_kernel(Args a) {
       const unsigned qc = qo < qo_last ? qo : qo_last;
       qo += q_step;
 #pragma unroll
-      for (int h = 0; h < H; ++h) T.qa[h] = *reinterpret_cast<const f4*>(P.q + qc + h * HD) * a.scale;
+      for (int j = 0; j < J; ++j) T.qa[j] = *reinterpret_cast<const f4*>(P.q + qc + j * TILE) * a.scale;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const unsigned hc = ho[r] < ho_last ? ho[r] : ho_last;
@@ -161,7 +166,10 @@ __global__ __launch_bounds__(TPB) void attn_node_scores_kernel(Args a) {
       for (int h = 0; h < H; ++h) {
         f4 s = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int x = 0; x < 4; ++x) s = mfma(cur.qa[h][x], kk[h][x], s);
+        for (int c = 0; c < M; ++c) {
+#pragma unroll
+          for (int x = 0; x < 4; ++x) s = mfma(cur.qa[h * M + c][x], kk[h * M + c][x], s);
+        }
 #pragma unroll
         for (int r = 0; r < 4; ++r) w[r] += fexp(fminf(s[r] - cur.lse[r][h], 0.f));   // a probability: never above 1
       }
@@ -194,20 +202,33 @@ __global__ __launch_bounds__(TPB) void attn_node_scores_kernel(Args a) {
   P.out_max[kr] = m * invh;                                       // a positive factor: commutes with the maximum
 }
 
-template <int H>
+template <int H, int M>
 int launch_scores(unsigned grid, hipStream_t st, const Args& a) {
-  return launch<attn_node_scores_kernel<H>>(dim3(grid), dim3(TPB), 0, st, a);
+  return launch<attn_node_scores_kernel<H, M>>(dim3(grid), dim3(TPB), 0, st, a);
 }
 
-}  // namespace
+// heads 1 .. MAX_H / M of head_dim 16 M (the caller has checked the range)
+template <int M>
+int launch_heads(int heads, unsigned grid, hipStream_t st, const Args& a) {
+  switch (heads) {
+    case 1: return launch_scores<1, M>(grid, st, a);
+    case 2: return launch_scores<2, M>(grid, st, a);
+    case 3: if constexpr (3 * M <= MAX_H) return launch_scores<3, M>(grid, st, a); break;
+    case 4: if constexpr (4 * M <= MAX_H) return launch_scores<4, M>(grid, st, a); break;
+    case 5: if constexpr (5 * M <= MAX_H) return launch_scores<5, M>(grid, st, a); break;
+    case 6: if constexpr (6 * M <= MAX_H) return launch_scores<6, M>(grid, st, a); break;
+    case 7: if constexpr (7 * M <= MAX_H) return launch_scores<7, M>(grid, st, a); break;
+    case 8: if constexpr (8 * M <= MAX_H) return launch_scores<8, M>(grid, st, a); break;
+  }
+  return CGVP_ERR_UNSUPPORTED_DIMS;
+}
 
-extern "C" int cgvp_attn_score_version(void) { return CGVP_ATTN_SCORE_VERSION; }
-
-extern "C" int cgvp_attn_node_scores(const cgvp_attn_score_problem* probs, int32_t num_problems, int64_t num_pairs,
-                                     int32_t heads, float scale, void* stream) {
+int node_scores(const cgvp_attn_score_problem* probs, int32_t num_problems, int64_t num_pairs, int32_t heads, int M,
+                float scale, void* stream) {
   if (!probs || num_problems < 1 || num_problems > 2 || num_pairs < 0 || num_pairs >= ((int64_t)1 << 30) || heads < 1)
     return CGVP_ERR_BAD_ARG;
-  if (heads > MAX_H) return CGVP_ERR_UNSUPPORTED_DIMS;
+  if ((int64_t)heads * M > MAX_H) return CGVP_ERR_UNSUPPORTED_DIMS;
+  const int HD = TILE * M;
   Args a;
   a.nprob = num_problems; a.B = (int)num_pairs; a.scale = scale;
   // the problem whose key tiles walk the most queries gets the low workgroup indices (they start first), as the
@@ -234,16 +255,27 @@ extern "C" int cgvp_attn_node_scores(const cgvp_attn_score_problem* probs, int32
   const unsigned grid = (unsigned)((int64_t)a.p[0].units + a.p[1].units);
   hipStream_t st = (hipStream_t)stream;
   int rc = 0;
-  switch (heads) {
-    case 1: rc = launch_scores<1>(grid, st, a); break;
-    case 2: rc = launch_scores<2>(grid, st, a); break;
-    case 3: rc = launch_scores<3>(grid, st, a); break;
-    case 4: rc = launch_scores<4>(grid, st, a); break;
-    case 5: rc = launch_scores<5>(grid, st, a); break;
-    case 6: rc = launch_scores<6>(grid, st, a); break;
-    case 7: rc = launch_scores<7>(grid, st, a); break;
-    default: rc = launch_scores<8>(grid, st, a); break;
+  switch (M) {
+    case 1: rc = launch_heads<1>(heads, grid, st, a); break;
+    case 2: rc = launch_heads<2>(heads, grid, st, a); break;
+    default: rc = launch_heads<4>(heads, grid, st, a); break;
   }
   if (rc) return rc;
   return launch_status();
+}
+
+}  // namespace
+
+extern "C" int cgvp_attn_score_version(void) { return CGVP_ATTN_SCORE_VERSION; }
+
+extern "C" int cgvp_attn_node_scores(const cgvp_attn_score_problem* probs, int32_t num_problems, int64_t num_pairs,
+                                     int32_t heads, float scale, void* stream) {
+  return node_scores(probs, num_problems, num_pairs, heads, 1, scale, stream);
+}
+
+// ---- include/caster_gvp_attnhd.h
+extern "C" int cgvp_attn_node_scores_hd(const cgvp_attn_score_problem* probs, int32_t num_problems, int64_t num_pairs,
+                                        int32_t heads, int32_t head_dim, float scale, void* stream) {
+  if (head_dim != 16 && head_dim != 32 && head_dim != 64) return CGVP_ERR_UNSUPPORTED_DIMS;
+  return node_scores(probs, num_problems, num_pairs, heads, head_dim / 16, scale, stream);
 }

@@ -22,10 +22,12 @@
 #include <c10/hip/HIPStream.h>
 
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <map>
 
 #include "../../include/caster_gvp.h"
+#include "../../include/caster_gvp_attnhd.h"
 
 namespace {
 
@@ -771,34 +773,55 @@ struct CrossAttention : public Function<CrossAttention> {
     P[1].q_ptr = (const int64_t*)aptr.data_ptr(); P[1].k_ptr = (const int64_t*)rptr.data_ptr();
     P[1].num_q = q_a.size(0); P[1].num_k = k_r.size(0);
   }
+  // Both directions in ONE launch when their head dims agree, else one launch each on the same stream; scale = 1 / sqrt(head_dim)
+  template <class Fn>
+  static void launch(Fn fn, const char* what, const cgvp_attn_problem* P, int64_t B, int64_t heads, const int64_t (&hd)[2], void* st) {
+    if (hd[0] == hd[1]) {
+      check(fn(P, 2, B, (int32_t)heads, (int32_t)hd[0], 1.0f / std::sqrt((float)hd[0]), nullptr, st), what);
+      return;
+    }
+    for (int i = 0; i < 2; ++i) check(fn(P + i, 1, B, (int32_t)heads, (int32_t)hd[i], 1.0f / std::sqrt((float)hd[i]), nullptr, st), what);
+  }
   static variable_list forward(AutogradContext* ctx, at::Tensor q_r_, at::Tensor k_a_, at::Tensor v_a_, at::Tensor q_a_, at::Tensor k_r_,
                                at::Tensor v_r_, at::Tensor rptr_, at::Tensor aptr_, int64_t heads) {
-    const int64_t E = heads * 16;
     at::Tensor t[6] = {rows_f32(q_r_, "q_r"), rows_f32(k_a_, "k_a"), rows_f32(v_a_, "v_a"), rows_f32(q_a_, "q_a"),
                        rows_f32(k_r_, "k_r"), rows_f32(v_r_, "v_r")};
-    for (const at::Tensor& x : t)
-      if (x.dim() != 2 || x.size(1) != E) throw NotImplemented("cross_attention: the kernels are compiled for head_dim 16 (embed = 16 * heads)");
+    // head_dim = width / heads per direction: (q_r, k_a, v_a) share one width, (q_a, k_r, v_r) another
+    int64_t hd[2];
+    for (int i = 0; i < 2; ++i) {
+      const at::Tensor& q = t[3 * i];
+      hd[i] = q.dim() == 2 && heads >= 1 && q.size(1) % heads == 0 ? q.size(1) / heads : 0;
+      if (hd[i] != 16 && hd[i] != 32 && hd[i] != 64)
+        throw NotImplemented("cross_attention: the kernels are compiled for head_dim 16, 32 and 64 (embed = heads * head_dim)");
+      for (int j = 1; j < 3; ++j)
+        if (t[3 * i + j].dim() != 2 || t[3 * i + j].size(1) != q.size(1))
+          throw NotImplemented("cross_attention: keys and values have the width of their queries");
+    }
+    const int64_t E_r = heads * hd[0], E_a = heads * hd[1];
     TORCH_CHECK(t[0].size(0) == t[4].size(0) && t[0].size(0) == t[5].size(0) && t[3].size(0) == t[1].size(0) && t[3].size(0) == t[2].size(0),
                 "row counts of the residue / atom tensors disagree");
     at::Tensor rptr = rptr_.to(at::kLong).contiguous(), aptr = aptr_.to(at::kLong).contiguous();
     TORCH_CHECK(rptr.is_cuda() && aptr.is_cuda() && rptr.dim() == 1 && rptr.sizes() == aptr.sizes() && rptr.numel() >= 1,
                 "rptr / aptr must both be [num_pairs + 1] on the GPU");
     const int64_t N = t[0].size(0), Na = t[3].size(0), B = rptr.numel() - 1;
-    at::Tensor o_r = at::empty({N, E}, t[0].options()), o_a = at::empty({Na, E}, t[0].options());
+    at::Tensor o_r = at::empty({N, E_r}, t[0].options()), o_a = at::empty({Na, E_a}, t[0].options());
     at::Tensor lse_r = at::empty({N, heads}, t[0].options()), lse_a = at::empty({Na, heads}, t[0].options());
     cgvp_attn_problem P[2];
     fill(P, t[0], t[1], t[2], t[3], t[4], t[5], rptr, aptr);
     P[0].out = (float*)ptr(o_r); P[0].lse = (float*)ptr(lse_r);
     P[1].out = (float*)ptr(o_a); P[1].lse = (float*)ptr(lse_a);
-    check(cgvp_attn_fwd(P, 2, B, (int32_t)heads, 0.25f, current_stream(t[0])), "cgvp_attn_fwd");
+    launch(cgvp_attn_fwd_hd, "cgvp_attn_fwd_hd", P, B, heads, hd, current_stream(t[0]));
     ctx->save_for_backward({t[0], t[1], t[2], t[3], t[4], t[5], o_r, o_a, lse_r, lse_a, rptr, aptr});
     ctx->saved_data["heads"] = heads;
+    ctx->saved_data["head_dim_r"] = hd[0];
+    ctx->saved_data["head_dim_a"] = hd[1];
     ctx->mark_non_differentiable({lse_r, lse_a});
     return {o_r, o_a, lse_r, lse_a};
   }
   static variable_list backward(AutogradContext* ctx, variable_list go) {
     auto sv = ctx->get_saved_variables();
     const int64_t heads = ctx->saved_data["heads"].toInt();
+    const int64_t hd[2] = {ctx->saved_data["head_dim_r"].toInt(), ctx->saved_data["head_dim_a"].toInt()};
     at::Tensor g_o_r = go[0].defined() ? rows_f32(go[0], "d o_r") : at::zeros_like(sv[6]);
     at::Tensor g_o_a = go[1].defined() ? rows_f32(go[1], "d o_a") : at::zeros_like(sv[7]);
     at::Tensor outs[6];
@@ -810,7 +833,7 @@ struct CrossAttention : public Function<CrossAttention> {
     P[0].g_q = (float*)ptr(outs[0]); P[0].g_k = (float*)ptr(outs[1]); P[0].g_v = (float*)ptr(outs[2]);
     P[1].out = (float*)ptr(sv[7]); P[1].lse = (float*)ptr(sv[9]); P[1].g_out = (const float*)ptr(g_o_a); P[1].delta = (float*)ptr(d_a);
     P[1].g_q = (float*)ptr(outs[3]); P[1].g_k = (float*)ptr(outs[4]); P[1].g_v = (float*)ptr(outs[5]);
-    check(cgvp_attn_bwd(P, 2, sv[10].numel() - 1, (int32_t)heads, 0.25f, current_stream(sv[0])), "cgvp_attn_bwd");
+    launch(cgvp_attn_bwd_hd, "cgvp_attn_bwd_hd", P, sv[10].numel() - 1, heads, hd, current_stream(sv[0]));
     // the two directions share no operand: a residue-side tensor gets its gradient from exactly one of them
     return {outs[0], outs[1], outs[2], outs[3], outs[4], outs[5], at::Tensor(), at::Tensor(), at::Tensor()};
   }

@@ -4,10 +4,12 @@
 (joint_gnn.py:321-409) that lies between their input and output projections, for BOTH directions in one launch, on
 compact row arrays with ptr offsets (no to_dense_batch padding, no key-padding masks, no score tensor in HBM):
 
-    o_r[q] = softmax_k(q_r[q] . k_a[k] / sqrt(16)) v_a[k]      residues attend to the atoms of their pair
-    o_a[q] = softmax_k(q_a[q] . k_r[k] / sqrt(16)) v_r[k]      atoms attend to the residues of their pair
+    o_r[q] = softmax_k(q_r[q] . k_a[k] / sqrt(head_dim)) v_a[k]      residues attend to the atoms of their pair
+    o_a[q] = softmax_k(q_a[q] . k_r[k] / sqrt(head_dim)) v_r[k]      atoms attend to the residues of their pair
 
-The projections themselves stay plain library GEMMs (F.linear on [N, 128] rows).  Registered with fake kernels,
+head_dim = width // heads is 16, 32 or 64 (include/caster_gvp_attnhd.h), per direction: (q_r, k_a, v_a) have one width
+and (q_a, k_r, v_r) another.  Equal widths go in one launch, unequal ones in one launch each on the same stream.
+The projections themselves stay plain library GEMMs (F.linear on [N, E] rows).  Registered with fake kernels,
 autograd (the backward is the op `cross_attention_backward`: two launches, no atomics) and an autocast rule (fp32),
 like the encoders.  `cross_attention_weights` produces nn.MultiheadAttention's head-averaged weights in the
 reference's dense [B, Lq_max, Lk_max] layout for inference (inference/evaluation.py:43-66).
@@ -25,7 +27,31 @@ from torch import Tensor
 from . import _lib
 from .ops import _f32, _ptr, _stream
 
-HEAD_DIM = 16
+HEAD_DIM = 16                # the shipped module: embed 128, 8 heads
+HEAD_DIMS = (16, 32, 64)     # what the kernels are compiled for
+
+# include/caster_gvp_attnhd.h: every attention entry point with the head width as an argument -- a header, a version
+# and a signature table of their own, bound on the handle of `_lib.lib()`.  (cgvp_attn_node_scores_hd takes the problem
+# struct of gvp_hip.attention_scores, which types it there.)
+ATTN_HD_VERSION = 1          # CGVP_ATTN_HD_VERSION
+_HD_ARGS = [C.POINTER(_lib.AttnProblem), C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_float]
+_HD_SIGNATURES = {
+    "cgvp_attn_hd_version": (C.c_int, []),
+    "cgvp_attn_fwd_hd": (C.c_int, _HD_ARGS + [C.POINTER(_lib.Rng), C.c_void_p]),
+    "cgvp_attn_bwd_hd": (C.c_int, _HD_ARGS + [C.POINTER(_lib.Rng), C.c_void_p]),
+    "cgvp_attn_weights_hd": (C.c_int, _HD_ARGS + [C.c_void_p]),
+}
+
+
+def hd_exported_symbols():
+    """Names include/caster_gvp_attnhd.h declares."""
+    return tuple(_HD_SIGNATURES) + ("cgvp_attn_node_scores_hd",)
+
+
+@functools.lru_cache(maxsize=None)
+def hd_lib():
+    """libcaster_gvp.so (the handle of `_lib.lib()`) with the head-width entry points typed (once)."""
+    return _lib.bind(_lib.lib(), _HD_SIGNATURES, "cgvp_attn_hd_version", ATTN_HD_VERSION, "attention head-width version")
 
 
 def _i64c(t, name):
@@ -43,7 +69,19 @@ def _problems(q_r, k_a, v_a, q_a, k_r, v_r, rptr, aptr):
     return P
 
 
+def head_dim_of(t, name, heads):
+    """width // heads of a [rows, width] operand; NotImplementedError unless it is one of HEAD_DIMS."""
+    hd, rest = divmod(int(t.shape[1]), heads) if t.dim() == 2 and heads >= 1 else (0, 1)
+    if rest or hd not in HEAD_DIMS:
+        raise NotImplementedError(f"{name}: the attention kernels are compiled for head_dim 16, 32 and 64 "
+                                  f"(embed = heads * head_dim), got {tuple(t.shape)} with {heads} heads")
+    return hd
+
+
 def _check(q_r, k_a, v_a, q_a, k_r, v_r, rptr, aptr, heads):
+    """The check of the shipped head shape alone: every operand is [rows, 16 * heads].  No op calls it any more (they take
+    `_check_hd`); it is kept because tests/test_attention_edges.py holds it to its refusals, one of which (4 heads at
+    width 128) is a shape `_check_hd` accepts.  It can go when that test may change."""
     E = heads * HEAD_DIM
     for name, t in (("q_r", q_r), ("k_a", k_a), ("v_a", v_a), ("q_a", q_a), ("k_r", k_r), ("v_r", v_r)):
         if t.dim() != 2 or t.shape[1] != E:
@@ -55,22 +93,49 @@ def _check(q_r, k_a, v_a, q_a, k_r, v_r, rptr, aptr, heads):
         raise ValueError("rptr / aptr must both be [num_pairs + 1]")
 
 
+def _check_hd(q_r, k_a, v_a, q_a, k_r, v_r, rptr, aptr, heads):
+    """-> (head_dim of the residue-query direction, head_dim of the atom-query direction), each of HEAD_DIMS."""
+    hds = []
+    for (qn, q), others in ((("q_r", q_r), (("k_a", k_a), ("v_a", v_a))), (("q_a", q_a), (("k_r", k_r), ("v_r", v_r)))):
+        hds.append(head_dim_of(q, qn, heads))
+        for name, t in others:
+            if t.dim() != 2 or t.shape[1] != q.shape[1]:
+                raise NotImplementedError(f"{name}: keys and values have the width of their queries "
+                                          f"({qn}: {q.shape[1]} = {heads} heads x head_dim {hds[-1]}), got {tuple(t.shape)}")
+    if not (q_r.shape[0] == k_r.shape[0] == v_r.shape[0] and q_a.shape[0] == k_a.shape[0] == v_a.shape[0]):
+        raise ValueError("row counts of the residue / atom tensors disagree")
+    if rptr.shape != aptr.shape or rptr.dim() != 1 or rptr.numel() < 1:
+        raise ValueError("rptr / aptr must both be [num_pairs + 1]")
+    return tuple(hds)
+
+
+def _launch(name, P, B, heads, hds, R=None):
+    """The entry point `name` of caster_gvp_attnhd.h on both directions: ONE launch with two problems when their head
+    dims agree, else one launch with one problem each, on the same stream.  scale = 1 / sqrt(head_dim)."""
+    fn = getattr(hd_lib(), name)
+    for first, n in (((0, 2),) if hds[0] == hds[1] else ((0, 1), (1, 1))):
+        args = [C.pointer(P[first]), n, B, heads, hds[first], 1.0 / math.sqrt(hds[first])]
+        if name != "cgvp_attn_weights_hd":
+            args.append(None if R is None else C.pointer(R[first]))
+        _lib.check(fn(*args, _stream()), name)
+
+
 @torch.library.custom_op("caster_gvp::cross_attention", mutates_args=(), device_types="cuda")
 def cross_attention_op(q_r: Tensor, k_a: Tensor, v_a: Tensor, q_a: Tensor, k_r: Tensor, v_r: Tensor, rptr: Tensor,
                        aptr: Tensor, heads: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """-> (o_r [N, E], o_a [Na, E], lse_r [N, heads], lse_a [Na, heads])."""
-    _check(q_r, k_a, v_a, q_a, k_r, v_r, rptr, aptr, heads)
+    hds = _check_hd(q_r, k_a, v_a, q_a, k_r, v_r, rptr, aptr, heads)
     ts = [_f32(t, "attention operand") for t in (q_r, k_a, v_a, q_a, k_r, v_r)]
     rptr, aptr = _i64c(rptr, "rptr"), _i64c(aptr, "aptr")
     dev = ts[0].device
     N, Na, B = int(q_r.shape[0]), int(q_a.shape[0]), int(rptr.numel()) - 1
     f32 = dict(dtype=torch.float32, device=dev)
-    o_r, o_a = torch.empty(N, heads * HEAD_DIM, **f32), torch.empty(Na, heads * HEAD_DIM, **f32)
+    o_r, o_a = torch.empty(N, heads * hds[0], **f32), torch.empty(Na, heads * hds[1], **f32)
     lse_r, lse_a = torch.empty(N, heads, **f32), torch.empty(Na, heads, **f32)
     P = _problems(*ts, rptr, aptr)
     P[0].out, P[0].lse, P[1].out, P[1].lse = _ptr(o_r).value or 0, _ptr(lse_r).value or 0, _ptr(o_a).value or 0, _ptr(lse_a).value or 0
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().cgvp_attn_fwd(P, 2, B, heads, 1.0 / math.sqrt(HEAD_DIM), _stream()), "cgvp_attn_fwd")
+        _launch("cgvp_attn_fwd_hd", P, B, heads, hds)
     return o_r, o_a, lse_r, lse_a
 
 
@@ -87,6 +152,7 @@ def cross_attention_backward_op(g_o_r: Tensor, g_o_a: Tensor, q_r: Tensor, k_a: 
                                 rptr: Tensor, aptr: Tensor,
                                 heads: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
     """-> (g_q_r, g_k_a, g_v_a, g_q_a, g_k_r, g_v_r)."""
+    hds = (head_dim_of(q_r, "q_r", heads), head_dim_of(q_a, "q_a", heads))      # (the forward checked the rest)
     ts = [_f32(t, "attention operand") for t in (q_r, k_a, v_a, q_a, k_r, v_r)]
     g_o_r, g_o_a, o_r, o_a = (_f32(t, "attention gradient") for t in (g_o_r, g_o_a, o_r, o_a))
     lse_r, lse_a = _f32(lse_r, "lse"), _f32(lse_a, "lse")
@@ -102,7 +168,7 @@ def cross_attention_backward_op(g_o_r: Tensor, g_o_a: Tensor, q_r: Tensor, k_a: 
     P[1].out, P[1].lse, P[1].g_out, P[1].delta = v(o_a), v(lse_a), v(g_o_a), v(d_a)
     P[1].g_q, P[1].g_k, P[1].g_v = v(outs[3]), v(outs[4]), v(outs[5])
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().cgvp_attn_bwd(P, 2, B, heads, 1.0 / math.sqrt(HEAD_DIM), _stream()), "cgvp_attn_bwd")
+        _launch("cgvp_attn_bwd_hd", P, B, heads, hds)
     return tuple(outs)
 
 
@@ -176,22 +242,21 @@ def cross_attention_dropout_op(q_r: Tensor, k_a: Tensor, v_a: Tensor, q_a: Tenso
                                aptr: Tensor, heads: int, pair: Tensor, site_r: int, site_a: int, p_r: float,
                                p_a: float) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """`cross_attention` with dropout on the softmax probabilities (nn.MultiheadAttention in training mode):
-    o = (softmax(q k^T / 4) o f) v, f in {0, 1/(1-p)} a pure function of (pair, site, head, query row, key row).
+    o = (softmax(q k^T / sqrt(head_dim)) o f) v, f in {0, 1/(1-p)} a pure function of (pair, site, head, query row, key row).
     -> (o_r, o_a, lse_r, lse_a); the lse are those of the UNdropped scores.  p_r = p_a = 0 is `cross_attention`."""
-    _check(q_r, k_a, v_a, q_a, k_r, v_r, rptr, aptr, heads)
+    hds = _check_hd(q_r, k_a, v_a, q_a, k_r, v_r, rptr, aptr, heads)
     ts = [_f32(t, "attention operand") for t in (q_r, k_a, v_a, q_a, k_r, v_r)]
     rptr, aptr = _i64c(rptr, "rptr"), _i64c(aptr, "aptr")
     dev = ts[0].device
     N, Na, B = int(q_r.shape[0]), int(q_a.shape[0]), int(rptr.numel()) - 1
     f32 = dict(dtype=torch.float32, device=dev)
-    o_r, o_a = torch.empty(N, heads * HEAD_DIM, **f32), torch.empty(Na, heads * HEAD_DIM, **f32)
+    o_r, o_a = torch.empty(N, heads * hds[0], **f32), torch.empty(Na, heads * hds[1], **f32)
     lse_r, lse_a = torch.empty(N, heads, **f32), torch.empty(Na, heads, **f32)
     P = _problems(*ts, rptr, aptr)
     P[0].out, P[0].lse, P[1].out, P[1].lse = _ptr(o_r).value or 0, _ptr(lse_r).value or 0, _ptr(o_a).value or 0, _ptr(lse_a).value or 0
     R = _rngs(pair, site_r, site_a, p_r, p_a)
     with torch.cuda.device(dev):
-        _lib.check(dropout_lib().cgvp_attn_fwd_dropout(P, 2, B, heads, 1.0 / math.sqrt(HEAD_DIM), R, _stream()),
-                   "cgvp_attn_fwd_dropout")
+        _launch("cgvp_attn_fwd_hd", P, B, heads, hds, R)
     return o_r, o_a, lse_r, lse_a
 
 
@@ -208,6 +273,7 @@ def cross_attention_dropout_backward_op(g_o_r: Tensor, g_o_a: Tensor, q_r: Tenso
                                         rptr: Tensor, aptr: Tensor, heads: int, pair: Tensor, site_r: int, site_a: int,
                                         p_r: float, p_a: float) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
     """-> (g_q_r, g_k_a, g_v_a, g_q_a, g_k_r, g_v_r); `pair`, sites and p are the forward's: the factors are regenerated."""
+    hds = (head_dim_of(q_r, "q_r", heads), head_dim_of(q_a, "q_a", heads))      # (the forward checked the rest)
     ts = [_f32(t, "attention operand") for t in (q_r, k_a, v_a, q_a, k_r, v_r)]
     g_o_r, g_o_a, o_r, o_a = (_f32(t, "attention gradient") for t in (g_o_r, g_o_a, o_r, o_a))
     lse_r, lse_a = _f32(lse_r, "lse"), _f32(lse_a, "lse")
@@ -224,8 +290,7 @@ def cross_attention_dropout_backward_op(g_o_r: Tensor, g_o_a: Tensor, q_r: Tenso
     P[1].g_q, P[1].g_k, P[1].g_v = v(outs[3]), v(outs[4]), v(outs[5])
     R = _rngs(pair, site_r, site_a, p_r, p_a)
     with torch.cuda.device(dev):
-        _lib.check(dropout_lib().cgvp_attn_bwd_dropout(P, 2, B, heads, 1.0 / math.sqrt(HEAD_DIM), R, _stream()),
-                   "cgvp_attn_bwd_dropout")
+        _launch("cgvp_attn_bwd_hd", P, B, heads, hds, R)
     return tuple(outs)
 
 
@@ -264,6 +329,7 @@ def cross_attention_weights_op(q_r: Tensor, k_a: Tensor, lse_r: Tensor, q_a: Ten
                                a_max: int) -> Tuple[Tensor, Tensor]:
     """-> (w_r [B, r_max, a_max], w_a [B, a_max, r_max]): head-averaged attention weights, zero in the padding.
     A pair with more than r_max residues or a_max atoms is truncated to the layout (its kept entries unchanged)."""
+    hds = _check_hd(q_r, k_a, k_a, q_a, k_r, k_r, rptr, aptr, heads)
     ts = [_f32(t, "attention operand") for t in (q_r, k_a, k_a, q_a, k_r, k_r)]
     lse_r, lse_a = _f32(lse_r, "lse"), _f32(lse_a, "lse")
     rptr, aptr = _i64c(rptr, "rptr"), _i64c(aptr, "aptr")
@@ -279,7 +345,7 @@ def cross_attention_weights_op(q_r: Tensor, k_a: Tensor, lse_r: Tensor, q_a: Ten
     P[0].out, P[0].lse, P[0].weights, P[0].weights_lq, P[0].weights_lk = v(dummy_r), v(lse_r), v(w_r), r_max, a_max
     P[1].out, P[1].lse, P[1].weights, P[1].weights_lq, P[1].weights_lk = v(dummy_a), v(lse_a), v(w_a), a_max, r_max
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().cgvp_attn_weights(P, 2, B, heads, 1.0 / math.sqrt(HEAD_DIM), _stream()), "cgvp_attn_weights")
+        _launch("cgvp_attn_weights_hd", P, B, heads, hds)
     return w_r, w_a
 
 

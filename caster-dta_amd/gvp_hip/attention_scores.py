@@ -21,12 +21,13 @@ from typing import List, Tuple
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _lib, attention_ops
 from ._lib import _on_gpu, _ptr, _stream
 
 ATTN_SCORE_VERSION = 1   # CGVP_ATTN_SCORE_VERSION
 MAX_HEADS = 8            # CGVP_ATTN_SCORE_MAX_HEADS
 HEAD_DIM = 16
+MAX_WIDTH = MAX_HEADS * HEAD_DIM   # the kernel keeps the keys of all heads in registers: heads * head_dim <= 128
 
 
 class ScoreProblem(C.Structure):
@@ -53,12 +54,34 @@ def lib():
     return _lib.bind(_lib.lib(), _SIGNATURES, "cgvp_attn_score_version", ATTN_SCORE_VERSION, "attention-score version")
 
 
+# include/caster_gvp_attnhd.h: the same kernel with the head width as an argument (the other entry points of that
+# header are typed in gvp_hip.attention_ops, on the same handle)
+_HD_SIGNATURES = {
+    "cgvp_attn_node_scores_hd": (C.c_int, [C.POINTER(ScoreProblem), _I32, _I64, _I32, _I32, C.c_float, _P]),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def hd_lib():
+    return _lib.bind(attention_ops.hd_lib(), _HD_SIGNATURES)
+
+
 def _rows(t, name, width):
     _on_gpu(t, name)
     if t.dim() != 2 or t.shape[1] != width:
-        raise NotImplementedError(f"{name}: the attention-score kernel is compiled for head_dim {HEAD_DIM} "
-                                  f"(expected [rows, {width}]), got {tuple(t.shape)}")
+        raise NotImplementedError(f"{name}: expected [rows, {width}] (the width of its direction's queries / the head "
+                                  f"count), got {tuple(t.shape)}")
     return t.detach().to(torch.float32).contiguous()
+
+
+def _width(q, name, heads):
+    """heads * head_dim of a direction's queries, head_dim in {16, 32, 64} and the width at most MAX_WIDTH."""
+    _on_gpu(q, name)
+    hd = attention_ops.head_dim_of(q, name, heads)
+    if heads * hd > MAX_WIDTH:
+        raise NotImplementedError(f"{name}: the attention-score kernel is compiled for embed widths up to {MAX_WIDTH} "
+                                  f"(heads * head_dim), got {heads} x {hd}; reduce caster_gvp::cross_attention_weights")
+    return heads * hd, hd
 
 
 def _offsets(t, name):
@@ -76,12 +99,15 @@ def cross_attention_node_scores_op(q_r: Tensor, k_a: Tensor, lse_r: Tensor, q_a:
     Direction 1: atom queries q_a, lse_a on residue keys k_r (protein_attention / max_protein_attention).  The
     operands and the lse are those of `caster_gvp::cross_attention`; rptr / aptr [B + 1] delimit the pairs.  A node
     whose pair has no node on the other side gets 0; rptr[-1] / aptr[-1] must be the row counts (rows behind them are
-    not written).  No host read, no synchronisation."""
+    not written).  No host read, no synchronisation.
+
+    head_dim = width // heads is 16, 32 or 64 per direction ((q_r, k_a) share a width, (q_a, k_r) another) and a width
+    is at most 128: NotImplementedError for anything else (the model then reduces the dense weights)."""
     if not 1 <= heads <= MAX_HEADS:
         raise NotImplementedError(f"the attention-score kernel is compiled for 1..{MAX_HEADS} heads, got {heads}")
-    E = heads * HEAD_DIM
-    q_r, k_r = _rows(q_r, "q_r", E), _rows(k_r, "k_r", E)
-    q_a, k_a = _rows(q_a, "q_a", E), _rows(k_a, "k_a", E)
+    (E_r, hd_r), (E_a, hd_a) = _width(q_r, "q_r", heads), _width(q_a, "q_a", heads)
+    q_r, k_a = _rows(q_r, "q_r", E_r), _rows(k_a, "k_a", E_r)
+    q_a, k_r = _rows(q_a, "q_a", E_a), _rows(k_r, "k_r", E_a)
     lse_r, lse_a = _rows(lse_r, "lse_r", heads), _rows(lse_a, "lse_a", heads)
     N, Na = int(q_r.shape[0]), int(q_a.shape[0])
     if not (k_r.shape[0] == lse_r.shape[0] == N and k_a.shape[0] == lse_a.shape[0] == Na):
@@ -101,9 +127,11 @@ def cross_attention_node_scores_op(q_r: Tensor, k_a: Tensor, lse_r: Tensor, q_a:
                                                      (q_a, k_r, lse_a, aptr, rptr, res_mean, res_max))):
         p.q, p.k, p.lse, p.q_ptr, p.k_ptr = v(q), v(k), v(lse), qp.data_ptr(), kp.data_ptr()
         p.num_q, p.num_k, p.out_mean, p.out_max = int(q.shape[0]), int(k.shape[0]), v(mean), v(mx)
+    fn = hd_lib().cgvp_attn_node_scores_hd
     with torch.cuda.device(dev):
-        rc = lib().cgvp_attn_node_scores(P, 2, B, heads, 1.0 / math.sqrt(HEAD_DIM), _stream())
-    _lib.check(rc, "cgvp_attn_node_scores")
+        # one launch for both directions when their head dims agree, else one each on the same stream
+        for first, n, hd in (((0, 2, hd_r),) if hd_r == hd_a else ((0, 1, hd_r), (1, 1, hd_a))):
+            _lib.check(fn(C.pointer(P[first]), n, B, heads, hd, 1.0 / math.sqrt(hd), _stream()), "cgvp_attn_node_scores_hd")
     return atom_mean, atom_max, res_mean, res_max
 
 

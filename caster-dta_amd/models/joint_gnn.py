@@ -12,7 +12,8 @@ by `batch`, then the affinity MLP.  With `ptr` offsets in the input dicts (what
 `forward_with_graphs` passes) the step has no data-dependent shape and no host
 synchronisation, so it captures into a HIP graph.  The reference's dense
 formulation (`to_dense_batch` + nn.MultiheadAttention) is kept for head shapes the
-kernel is not compiled for (head_dim != 16); attention dropout is drawn inside
+kernel is not compiled for (head_dim outside 16 / 32 / 64; the two directions may
+differ in width: one launch each then); attention dropout is drawn inside
 the kernel (`caster_gvp::cross_attention_dropout`).
 It does not import torch_geometric (`to_dense_batch` is restated below).
 
@@ -528,10 +529,11 @@ class CrossAttentionModule(nn.Module):
 
     # ------------------------------------------------------------ varlen path (MI355X kernel)
     def varlen_supported(self, rows):
-        """The varlen kernel is compiled for head_dim 16 on CUDA rows; attention dropout in training mode is drawn inside
-        it (caster_gvp::cross_attention_dropout)."""
+        """The varlen kernels are compiled for head_dim 16, 32 and 64 on CUDA rows; the two directions share the head
+        count and may differ in width (one launch each then).  Attention dropout in training mode is drawn inside the
+        kernels (caster_gvp::cross_attention_dropout).  Every other shape (head_dim 8, 48, ...) takes the dense path."""
         m1, m2 = self.embed1_to_2, self.embed2_to_1
-        return (rows.is_cuda and m1.head_dim == 16 and m2.head_dim == 16 and m1.embed_dim == m2.embed_dim
+        return (rows.is_cuda and m1.head_dim in (16, 32, 64) and m2.head_dim in (16, 32, 64)
                 and m1.num_heads == m2.num_heads)
 
     @staticmethod
@@ -572,7 +574,11 @@ class CrossAttentionModule(nn.Module):
         graph b of side 1 attends to graph b of side 2 and vice versa (joint_gnn.py:376-398).  The softmax(QK^T)V
         core of both directions is one launch of caster_gvp::cross_attention; projections and feed-forward are
         GEMMs on the compact rows.  Returns (embed_1, embed_2, (w1, w2) or None).  `scores_out`: a list this layer
-        appends its NodeAttention to (caster_gvp::cross_attention_node_scores: one launch, no host read).
+        appends its NodeAttention to (caster_gvp::cross_attention_node_scores: one launch, no host read).  The score
+        kernel is compiled for embed widths up to 128; a layer with a wider side (256 with 8 heads; with unequal widths
+        128 / 256 BOTH directions go this way) reduces the dense
+        caster_gvp::cross_attention_weights with `_dense_node_attention` instead, which reads the longest pair's
+        lengths on the host -- acceptable where scores are produced: at inference.
 
         In training mode with attention dropout > 0 the core is caster_gvp::cross_attention_dropout: the probabilities
         are dropped inside the kernels, from `sites.pair` when the row-wise sites are active and from a pair of this
@@ -584,15 +590,15 @@ class CrossAttentionModule(nn.Module):
             lanes = _Lanes(False, embed_1.device)
         # side 1 (residue rows) on the launch stream, side 2 (atom rows) on the other lane: each side's norm and the
         # projections that read it (its own queries, the OTHER direction's keys / values)
-        E = self.embed1_to_2.embed_dim
+        E1, E2 = self.embed1_to_2.embed_dim, self.embed2_to_1.embed_dim      # direction 1 -> 2 works in E1, 2 -> 1 in E2
         p12, p21 = self._proj_parts(self.embed1_to_2), self._proj_parts(self.embed2_to_1)
         n1 = fast_layer_norm(embed_1, self.preattn_norm1)
         q1 = self._q(p12, n1)
-        k2, v2 = self._kv(p21, n1, E)
+        k2, v2 = self._kv(p21, n1, E2)
         with lanes.atom():
             n2 = fast_layer_norm(embed_2, self.preattn_norm2)
             q2 = self._q(p21, n2)
-            k1, v1 = self._kv(p12, n2, E)
+            k1, v1 = self._kv(p12, n2, E1)
         lanes.join(q2, k1, v1)
         heads = self.embed1_to_2.num_heads
         from gvp_hip import head_ops
@@ -615,15 +621,27 @@ class CrossAttentionModule(nn.Module):
         a1 = fast_linear(o1, self.embed1_to_2.out_proj.weight, self.embed1_to_2.out_proj.bias)
         with lanes.atom():
             a2 = fast_linear(o2, self.embed2_to_1.out_proj.weight, self.embed2_to_1.out_proj.bias)
+        from gvp_hip import attention_scores  # noqa: F401  (registers the op)
+        dense_scores = scores_out is not None and max(E1, E2) > attention_scores.MAX_WIDTH
         weights = None
-        if need_weights:
+        if need_weights or dense_scores:
             l1 = int((ptr1[1:] - ptr1[:-1]).max()) if ptr1.numel() > 1 else 0      # inference only: host sync
             l2 = int((ptr2[1:] - ptr2[:-1]).max()) if ptr2.numel() > 1 else 0
             weights = tuple(torch.ops.caster_gvp.cross_attention_weights(q1.detach(), k1.detach(), lse1.detach(),
                                                                          q2.detach(), k2.detach(), lse2.detach(),
                                                                          ptr1, ptr2, heads, l1, l2))
-        if scores_out is not None:
-            from gvp_hip import attention_scores  # noqa: F401  (registers the op)
+        if dense_scores:
+            # wider than the score kernel: the same four vectors from the dense weights (their lengths were read above)
+            if l1 == 0 or l2 == 0:                      # a side without nodes: no weights at all, every score is 0
+                z1, z2 = embed_1.new_zeros(embed_1.shape[0]), embed_2.new_zeros(embed_2.shape[0])
+                scores_out.append(NodeAttention(z1, z1.clone(), z2, z2.clone()))
+            else:
+                n1_, n2_ = ptr1[1:] - ptr1[:-1], ptr2[1:] - ptr2[:-1]
+                mask1 = torch.arange(l1, device=ptr1.device)[None, :] < n1_[:, None]
+                mask2 = torch.arange(l2, device=ptr2.device)[None, :] < n2_[:, None]
+                scores_out.append(_dense_node_attention(weights[0], weights[1], mask1, mask2))
+            weights = weights if need_weights else None
+        elif scores_out is not None:
             atom_mean, atom_max, residue_mean, residue_max = torch.ops.caster_gvp.cross_attention_node_scores(
                 q1.detach(), k1.detach(), lse1.detach(), q2.detach(), k2.detach(), lse2.detach(), ptr1, ptr2, heads)
             scores_out.append(NodeAttention(residue_mean, residue_max, atom_mean, atom_max))
