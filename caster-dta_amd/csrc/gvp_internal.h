@@ -126,6 +126,30 @@ int gine_fwd(int cin, int chid, int cout, int nt, int net, int ed, const float* 
              const float* eattr, const int64_t* etypes, const int32_t* rowptr, const int32_t* eperm,
              const int32_t* esrc, const int32_t* edst, int64_t N, const cgvp_gine_w* w, float slope,
              const float* mask, gvp::RngArgs rng, float* out, float* agg_out, uint16_t* pos_out, hipStream_t st);
+// the same two over the shapes of gine_quad_wide_kernels.hip / gine_quad_wide64_kernels.hip (what gine_bwd / gine_fwd try
+// after their own table; same returns)
+int gine_bwd_wide(int cin, int chid, int cout, int nt, int net, int ed, const float* x, const int64_t* ntypes,
+                  const float* eattr, const int64_t* etypes, const int32_t* rowptr, const int32_t* eperm,
+                  const int32_t* esrc, const int32_t* edst, int64_t N, const cgvp_gine_w* w, float slope,
+                  const float* mask, gvp::RngArgs rng, const float* g_out, float* g_x, float* slab, int max_workgroups,
+                  int* rows, int* row_len, hipStream_t st, const float* agg_in, const uint16_t* pos_in, float* g_edge,
+                  float* g_self, float* g_eattr, int eattr_accum);
+int gine_fwd_wide(int cin, int chid, int cout, int nt, int net, int ed, const float* x, const int64_t* ntypes,
+                  const float* eattr, const int64_t* etypes, const int32_t* rowptr, const int32_t* eperm,
+                  const int32_t* esrc, const int32_t* edst, int64_t N, const cgvp_gine_w* w, float slope,
+                  const float* mask, gvp::RngArgs rng, float* out, float* agg_out, uint16_t* pos_out, hipStream_t st);
+int gine_bwd_wide64(int cin, int chid, int cout, int nt, int net, int ed, const float* x, const int64_t* ntypes,
+                  const float* eattr, const int64_t* etypes, const int32_t* rowptr, const int32_t* eperm,
+                  const int32_t* esrc, const int32_t* edst, int64_t N, const cgvp_gine_w* w, float slope,
+                  const float* mask, gvp::RngArgs rng, const float* g_out, float* g_x, float* slab, int max_workgroups,
+                  int* rows, int* row_len, hipStream_t st, const float* agg_in, const uint16_t* pos_in, float* g_edge,
+                  float* g_self, float* g_eattr, int eattr_accum);
+int gine_fwd_wide64(int cin, int chid, int cout, int nt, int net, int ed, const float* x, const int64_t* ntypes,
+                  const float* eattr, const int64_t* etypes, const int32_t* rowptr, const int32_t* eperm,
+                  const int32_t* esrc, const int32_t* edst, int64_t N, const cgvp_gine_w* w, float slope,
+                  const float* mask, gvp::RngArgs rng, float* out, float* agg_out, uint16_t* pos_out, hipStream_t st);
+bool gine_shape_compiled(int cin, int chid, int cout, int nt, int net, int ed);   // the tile kernels exist for the layer
+int gine_max_slab_row();                  // floats of the largest compiled layer's gradient block
 int reduce_slab(const float* slab, int rows, int stride, int col0, int len, float* dst, hipStream_t st);
 int reduce_segments(const cgvp_segment* segs, int nsegs, float* grad_params, hipStream_t st, int overwrite = 0,
                     bool store_only = false);

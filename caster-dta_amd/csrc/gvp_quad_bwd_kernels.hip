@@ -1401,8 +1401,10 @@ int src_sum(int width, const float* rows, const float* self, const int32_t* sptr
   switch (width) {
     case 16: return launch<src_sum_kernel<16>>(dim3(blocks), dim3(256), 0, st, a);
     case ROW: return launch<src_sum_kernel<ROW>>(dim3(blocks), dim3(256), 0, st, a);
+    case 32: return launch<src_sum_kernel<32>>(dim3(blocks), dim3(256), 0, st, a);      // GINE middle layers of width 32 / 64
     case 41: return launch<src_sum_kernel<41>>(dim3(blocks), dim3(256), 0, st, a);
     case 52: return launch<src_sum_kernel<52>>(dim3(blocks), dim3(256), 0, st, a);
+    case 64: return launch<src_sum_kernel<64>>(dim3(blocks), dim3(256), 0, st, a);
     default: return CGVP_ERR_UNSUPPORTED_DIMS;
   }
 }

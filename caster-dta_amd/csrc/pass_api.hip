@@ -118,10 +118,26 @@ int check_gine_cfg(const cgvp_gine_cfg* c) {
   if (c->widths[0] <= c->num_ntypes) return CGVP_ERR_BAD_ARG;
   return 0;
 }
+// every layer of the configuration has tile kernels (forward with saved state, backward): a training pass runs on nothing else
+int check_gine_shapes(const cgvp_gine_cfg* c) {
+  for (int l = 0; l < c->num_layers; ++l)
+    if (!quad::gine_shape_compiled(c->widths[l], c->widths[l + 1], c->widths[l + 1], l == 0 ? c->num_ntypes : 0, c->num_etypes,
+                                   c->edge_dim))
+      return CGVP_ERR_UNSUPPORTED_DIMS;
+  return 0;
+}
 struct GineBwdWs { int64_t slabs, gx, total, slab_floats, gx_floats; int det; DetWs det_ws; };   // extra: (1+eps) dh rows
 void gine_bwd_layout(const cgvp_gine_cfg* c, int64_t N, GineBwdWs* w, int64_t E = 0, bool det = false) {
   Bump b;
-  w->slab_floats = cgvp_gine_bwd_workspace_floats();
+  // kGineBwdMaxGrid slab rows of the configuration's largest layer, never fewer floats than the (16,64,64) layer of the
+  // shipped models takes: their workspace is what it always was, a wider stack gets the room its rows need
+  const int ke = c->num_etypes + c->edge_dim;
+  int row = gine_layer_floats(16, 64, 64, 14);
+  for (int l = 0; l < c->num_layers; ++l) {
+    const int r = gine_layer_floats(c->widths[l], c->widths[l + 1], c->widths[l + 1], ke);
+    row = r > row ? r : row;
+  }
+  w->slab_floats = (int64_t)quad::kGineBwdMaxGrid * row;
   w->slabs = b.take((int64_t)c->num_layers * w->slab_floats * 4);
   int maxw = 0;
   for (int l = 1; l < c->num_layers; ++l) maxw = c->widths[l] > maxw ? c->widths[l] : maxw;
@@ -464,6 +480,8 @@ int cgvp_gine_forward_pass(const cgvp_gine_cfg* cfg, const cgvp_gine_w* w, const
   cgvp_gine_fwd_ws ws;
   if (int rc = cgvp_gine_fwd_workspace(cfg, N, E, save_state, &ws)) return rc;
   if (!(dropout_p >= 0.f && dropout_p < 1.f)) return CGVP_ERR_BAD_ARG;
+  if (save_state)          // refused before the first launch: nothing is written
+    if (int rc = check_gine_shapes(cfg)) return rc;
   const int L = cfg->num_layers;
   const bool drop = dropout_p > 0.f && save_state && L > 1;
   const bool draw = drop && !masks;
@@ -495,8 +513,7 @@ int cgvp_gine_forward_pass(const cgvp_gine_cfg* cfg, const cgvp_gine_w* w, const
     bool done = false;
     if (save_state) {
       // training pass: the tile kernels (whatever `variant` says), which also SAVE the aggregated messages and their ReLU
-      // patterns for the backward (cgvp_gine_fwd_ws.agg / .pos); a width they are not compiled for takes the generic
-      // kernel below -- and has no backward kernel either
+      // patterns for the backward (cgvp_gine_fwd_ws.agg / .pos); every layer shape is a compiled one (checked above)
       if (((uintptr_t)x & 15) || ((uintptr_t)y & 15)) return CGVP_ERR_BAD_ARG;
       gvp::RngArgs ra{(dl && draw) ? reinterpret_cast<const unsigned long long*>(seed) : nullptr, dropout_p, l};
       if (!(dl && draw)) ra = gvp::RngArgs{nullptr, 0.f, 0};
@@ -560,6 +577,7 @@ int cgvp_gine_backward_pass_eattr(const cgvp_gine_cfg* cfg, const cgvp_gine_w* w
   const int64_t N = batch->num_nodes, E = batch->num_edges;
   cgvp_gine_fwd_ws ws;
   if (int rc = cgvp_gine_fwd_workspace(cfg, N, E, 1, &ws)) return rc;
+  if (int rc = check_gine_shapes(cfg)) return rc;
   GineBwdWs bw;
   gine_bwd_layout(cfg, N, &bw, E, det);
   const int L = cfg->num_layers;

@@ -9,8 +9,9 @@ checkpoints keep their keys (`conv_list.{l}.eps`, `.lin.{weight,bias}`,
 
     x'_i = act( Lin1( act( Lin0( (1 + eps) x_i + sum_{j->i} ReLU(x_j + W_e e_ji + b_e) ) ) ) )
 
-runs as ONE launch of libcaster_gvp.so per layer (16-atom MFMA tiles, csrc/gine_quad_kernels.hip), the whole encoder
-pass as one host call (cgvp_gine_forward_pass).  No eager/CPU fallback.
+runs as ONE launch of libcaster_gvp.so per layer (16-atom MFMA tiles, csrc/gine_quad_tile.h), the whole encoder
+pass as one host call (cgvp_gine_forward_pass).  No eager/CPU fallback: the kernels are compiled for hidden_channels and
+out_channels in GINE_WIDTHS over a 52-column first layer, and any other width is an error at the first forward.
 """
 import warnings
 from functools import partial
@@ -133,8 +134,17 @@ class GINEConv(nn.Module):
         return dict(eps=self.eps, we=we, be=self.lin.bias, w0=l0.weight, b0=l0.bias, w1=l1.weight, b1=l1.bias)
 
 
+GINE_WIDTHS = (16, 32, 64)      # hidden_channels / out_channels the GINE kernels are compiled for
+GINE_IN_WIDTH = 52              # ... behind a first layer of in_channels + atom-type columns = 41 + 11
+
+
 class HomoMoleculeGNN_GINE(BaseMoleculeGNN):
-    """GINE encoder over atom graphs: N x 41 atom features -> N x 64 atom embeddings."""
+    """GINE encoder over atom graphs: N x 41 atom features -> N x out_channels atom embeddings.
+
+    Compiled configurations: `hidden_channels` and `out_channels` each 16, 32 or 64 (GINE_WIDTHS), `num_convs` 1..8,
+    in_channels + atom-type columns = 52 (11 one-hot types or an 11-wide nn.Embedding in front of 41 features), 5 bond
+    types, 9 bond features.  CASTER-DTA ships hidden 16, out 64.  Anything else raises NotImplementedError at the first
+    forward; there is no fallback."""
 
     def __init__(self, act_first=False, gin_norm=None, gin_norm_kwargs=None, gin_trainable_eps=True, **kwargs):
         super().__init__(**kwargs)
@@ -198,6 +208,11 @@ class HomoMoleculeGNN_GINE(BaseMoleculeGNN):
             x = torch.cat([self.ntype_embedding(ntypes).to(x.dtype), x], dim=-1)
         if eattr is None:
             raise NotImplementedError("the GINE encoder needs edge features (eattr)")
+        bad = [w for w in self._widths[1:] if w not in GINE_WIDTHS]
+        if bad or self._widths[0] != GINE_IN_WIDTH:
+            raise NotImplementedError(
+                f"the fused GINE kernels are compiled for hidden_channels and out_channels in {GINE_WIDTHS} behind a "
+                f"{GINE_IN_WIDTH}-column first layer (in_channels + atom-type columns); got layer widths {self._widths}")
         if not x.is_cuda:
             raise RuntimeError(f"x: caster-dta_amd runs on MI355X only (got a {x.device} tensor); there is no CPU path")
         needs_grad = torch.is_grad_enabled() and (x.requires_grad or eattr.requires_grad

@@ -359,8 +359,8 @@ int cgvp_node_embed_bwd(const cgvp_dims* dims, const cgvp_layout* layout, const 
  * features [N][cin - num_ntypes] and `ntypes`, and the one-hot columns are
  * synthesised on the fly (molecule_gnn.py:127-140).  cin <= 64, chid <= 64,
  * cout <= 64, edge_dim + num_etypes <= 16.
- * variant 0 (production): 16-atom MFMA tiles (csrc/gine_quad_kernels.hip) for the
- * compiled CASTER-DTA layer shapes -- needs `edst` as well -- and the generic kernel for
+ * variant 0 (production): 16-atom MFMA tiles (csrc/gine_quad_tile.h) for the
+ * compiled layer shapes (listed at cgvp_gine_conv_bwd) -- needs `edst` as well -- and the generic kernel for
  * any other shape; variant 1: always the generic one-wave-per-atom kernel (`edst` may
  * be NULL), kept as the independent second implementation for cross-checks. */
 typedef struct {
@@ -388,9 +388,11 @@ int cgvp_gine_conv_fwd(const float* x, const int64_t* ntypes, int32_t num_ntypes
  * gradients ADDED into `grad_layer` in state_dict order
  *   eps | nn.lins.0.weight | nn.lins.0.bias | nn.lins.1.weight | nn.lins.1.bias | lin.weight | lin.bias.
  * Takes all four CSR tables of cgvp_csr_from_coo (the forward needs no edst).
- * Runs on 16-atom MFMA tiles (csrc/gine_quad_kernels.hip).  Compiled for the
- * CASTER-DTA layer shapes (52,16,16), (16,64,64), (16,16,16) with 11 / 0 atom
- * types, 5 bond types, 9 bond features. */
+ * Runs on 16-atom MFMA tiles (csrc/gine_quad_tile.h).  Compiled for the 15 layer
+ * shapes (cin, c, c) with c in {16, 32, 64}: cin = 52 with 11 / 0 atom types, and
+ * cin in {16, 32, 64} without; 5 bond types, 9 bond features.  Any other shape:
+ * CGVP_ERR_UNSUPPORTED_DIMS.  cgvp_gine_bwd_workspace_floats() covers the largest
+ * of them, (64,64,64), at the largest max_workgroups (256). */
 int64_t cgvp_gine_bwd_workspace_floats(void);
 /* `max_workgroups`: cap on the workgroups (= CUs) the backward may occupy; <= 0 selects the
  * default of 16: inside CASTER-DTA the drug backward runs beside the protein backward, whose
@@ -576,7 +578,9 @@ typedef struct {
 int cgvp_gine_fwd_workspace(const cgvp_gine_cfg* cfg, int64_t num_nodes, int64_t num_edges, int32_t save_state,
                             cgvp_gine_fwd_ws* out);
 /* w: HOST array of num_layers cgvp_gine_w; masks: NULL or HOST array of num_layers - 1 device pointers ([N][widths[l+1]],
- * explicit inter-layer dropout factors, test hook); otherwise dropout_p > 0 draws in-kernel from rng_state. */
+ * explicit inter-layer dropout factors, test hook); otherwise dropout_p > 0 draws in-kernel from rng_state.
+ * A training pass (save_state) runs on the tile kernels only: a layer shape outside the compiled set (see
+ * cgvp_gine_conv_bwd) returns CGVP_ERR_UNSUPPORTED_DIMS before the first launch, and so does the backward pass. */
 int cgvp_gine_forward_pass(const cgvp_gine_cfg* cfg, const cgvp_gine_w* w, const cgvp_gine_batch* batch,
                            float dropout_p, uint64_t* rng_state, const float* const* masks, int32_t* csr_counters,
                            void* workspace, int32_t save_state, int32_t variant, float* out, void* stream);
