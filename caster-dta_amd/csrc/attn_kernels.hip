@@ -36,26 +36,13 @@
 
 #include "../../include/caster_gvp_attndrop.h"
 #include "../../include/caster_gvp_attnhd.h"
-#include "gvp_host.h"
+#include "attn_common.h"
 #include "gvp_rng.h"
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-constexpr int WAVE = 64, TILE = 16, WPB = 4, TPB = WAVE * WPB;     // head_dim = TILE * M
-
-__device__ __forceinline__ f4 mfma(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-// exp through v_exp_f32 (2^x of x * log2 e): one multiply and one transcendental instead of expf's range reduction
-// (~12 VALU); every argument here is <= 0 or a difference from a saved log-sum-exp, nowhere near overflow.
-__device__ __forceinline__ float fexp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
-__device__ __forceinline__ float quad_max(float x) {
-  x = fmaxf(x, __shfl_xor(x, 16));
-  return fmaxf(x, __shfl_xor(x, 32));
-}
-__device__ __forceinline__ float quad_sum(float x) {
-  x += __shfl_xor(x, 16);
-  return x + __shfl_xor(x, 32);
-}
+using namespace attn;
+constexpr int WPB = 4, TPB = WAVE * WPB;
 
 struct Prob {
   const float* q; const float* k; const float* v;         // [Nq][E], [Nk][E], [Nk][E]
@@ -67,46 +54,6 @@ struct Prob {
   int32_t units_q, units_k;                                // upper bounds: (ceil(Nq/16) + B) and (ceil(Nk/16) + B)
 };
 struct Args { Prob p[2]; int nprob; int B; int H; int E; float scale; };
-
-// Which pair owns tile `t` when every pair b contributes ceil((ptr[b+1] - ptr[b]) / 16) consecutive tiles?
-// Wave-parallel prefix scan over the pairs, 64 at a time (B is a few dozen to a few hundred).  Returns false past
-// the last tile.  All lanes return the same (b, first row of the tile, end row of the pair).
-__device__ __forceinline__ bool locate(const int64_t* __restrict__ ptr, int B, int t, int lane, int& b, int64_t& row0,
-                                       int64_t& row_end) {
-  int base = 0;
-  for (int c = 0; c < B; c += WAVE) {
-    const int i = c + lane;
-    const int64_t lo = i < B ? ptr[i] : 0, hi = i < B ? ptr[i + 1] : 0;
-    const int tiles = (int)((hi - lo + TILE - 1) / TILE);
-    int incl = tiles;
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-      const int y = __shfl_up(incl, d);
-      if (lane >= d) incl += y;
-    }
-    const int total = __shfl(incl, WAVE - 1);
-    if (t < base + total) {
-      const bool mine = t >= base + incl - tiles && t < base + incl;
-      const unsigned long long vote = __ballot(mine);
-      const int src = __ffsll((long long)vote) - 1;
-      b = c + src;
-      const int first = __shfl(base + incl - tiles, src);
-      const int64_t plo = __shfl((long long)lo, src), phi = __shfl((long long)hi, src);
-      row0 = plo + (int64_t)(t - first) * TILE;
-      row_end = phi;
-      return true;
-    }
-    base += total;
-  }
-  return false;
-}
-
-// The problem a wave works on, BY VALUE and selected with a wave-uniform index: `const Prob& P = a.p[pi]` with an index the
-// compiler cannot prove uniform turned every P.k / P.v / ... inside the loops into a vector load of the pointer from the
-// kernel-argument segment followed by s_waitcnt vmcnt(0) -- five dependent load pairs per key tile, 70-83 us per launch
-// for 6 us of matrix work (profiles/r03/kernel_stats_davis_b64_joint_before.csv).
-__device__ __forceinline__ Prob pick(const Args& a, int pi) { return pi ? a.p[1] : a.p[0]; }
-__device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 
 // ------------------------------------------------------------------------------------------------ attention dropout
 // nn.MultiheadAttention's training arithmetic (include/caster_gvp_attndrop.h): the PROBABILITIES are dropped, after the
@@ -572,13 +519,10 @@ int fill(Args& a, const cgvp_attn_problem* probs, int nprob, int64_t B, int H, i
     p = Prob{};
     if (i >= nprob) continue;
     const cgvp_attn_problem& s = probs[swap ? 1 - i : i];
-    if (s.num_q < 0 || s.num_k < 0 || !s.q_ptr || !s.k_ptr) return CGVP_ERR_BAD_ARG;
-    if ((s.num_q + TILE) * ((int64_t)H * HD) >= ((int64_t)1 << 31) || (s.num_k + TILE) * ((int64_t)H * HD) >= ((int64_t)1 << 31))
-      return CGVP_ERR_BAD_ARG;                             // the kernels address rows with 32-bit element offsets
+    if (!side_ok(s.num_q, s.q_ptr, (int64_t)H * HD) || !side_ok(s.num_k, s.k_ptr, (int64_t)H * HD)) return CGVP_ERR_BAD_ARG;
     if (s.num_q > 0 && (!s.q || !s.out || !s.lse)) return CGVP_ERR_BAD_ARG;
     if (s.num_k > 0 && (!s.k || !s.v)) return CGVP_ERR_BAD_ARG;
-    const void* al[] = {s.q, s.k, s.v, s.out, s.g_out, s.g_q, s.g_k, s.g_v};
-    for (const void* x : al) if ((uintptr_t)x & 15) return CGVP_ERR_BAD_ARG;
+    if (!aligned(16, s.q, s.k, s.v, s.out, s.g_out, s.g_q, s.g_k, s.g_v)) return CGVP_ERR_BAD_ARG;
     p.q = s.q; p.k = s.k; p.v = s.v; p.q_ptr = s.q_ptr; p.k_ptr = s.k_ptr; p.out = s.out; p.lse = s.lse;
     p.g_out = s.g_out; p.delta = s.delta; p.g_q = s.g_q; p.g_k = s.g_k; p.g_v = s.g_v;
     p.w = s.weights; p.w_lq = s.weights_lq; p.w_lk = s.weights_lk;
@@ -609,17 +553,6 @@ int drop_of(Drop& d, const cgvp_rng* rng, int nprob, int H) {
 Drop ordered(const Drop& d, bool swap) {                          // in the order fill() gave the problems
   if (!swap) return d;
   return Drop{{d.seed[1], d.seed[0]}, {d.rule[1], d.rule[0]}, {d.stream[1], d.stream[0]}};
-}
-
-// head_dim -> M: `f` is called with std::integral_constant<int, M>; any other head_dim is refused before anything else.
-template <class F>
-int with_m(int head_dim, F&& f) {
-  switch (head_dim) {
-    case 16: return f(std::integral_constant<int, 1>{});
-    case 32: return f(std::integral_constant<int, 2>{});
-    case 64: return f(std::integral_constant<int, 4>{});
-    default: return CGVP_ERR_UNSUPPORTED_DIMS;
-  }
 }
 
 int attn_fwd(const cgvp_attn_problem* probs, int nprob, int64_t B, int H, int head_dim, float scale, const cgvp_rng* rng,

@@ -29,24 +29,12 @@
 
 #include "../../include/caster_gvp_attnhd.h"
 #include "../../include/caster_gvp_attnscore.h"
-#include "gvp_host.h"
+#include "attn_common.h"
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-constexpr int WAVE = 64, TILE = 16, WPB = 8, TPB = WAVE * WPB, MAX_H = CGVP_ATTN_SCORE_MAX_HEADS;
-
-__device__ __forceinline__ f4 mfma(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-// exp through v_exp_f32, as in attn_kernels.hip (the lse was produced with the same function)
-__device__ __forceinline__ float fexp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
-__device__ __forceinline__ float quad_max(float x) {
-  x = fmaxf(x, __shfl_xor(x, 16));
-  return fmaxf(x, __shfl_xor(x, 32));
-}
-__device__ __forceinline__ float quad_sum(float x) {
-  x += __shfl_xor(x, 16);
-  return x + __shfl_xor(x, 32);
-}
+using namespace attn;
+constexpr int WPB = 8, TPB = WAVE * WPB, MAX_H = CGVP_ATTN_SCORE_MAX_HEADS;
 
 struct Prob {
   const float* q; const float* k; const float* lse;       // [Nq][E], [Nk][E], [Nq][H]
@@ -55,44 +43,6 @@ struct Prob {
   int32_t units;                                           // upper bound of the key tiles: ceil(Nk / 16) + B
 };
 struct Args { Prob p[2]; int nprob; int B; float scale; };
-
-// Which pair owns tile `t` when every pair b contributes ceil((ptr[b+1] - ptr[b]) / 16) consecutive tiles?  The scan of
-// attn_kernels.hip (file-local there): wave-parallel over the pairs, 64 at a time, any B.  Returns false past the last
-// tile.  All lanes return the same (b, first row of the tile, end row of the pair).
-__device__ __forceinline__ bool locate(const int64_t* __restrict__ ptr, int B, int t, int lane, int& b, int64_t& row0,
-                                       int64_t& row_end) {
-  int base = 0;
-  for (int c = 0; c < B; c += WAVE) {
-    const int i = c + lane;
-    const int64_t lo = i < B ? ptr[i] : 0, hi = i < B ? ptr[i + 1] : 0;
-    const int tiles = (int)((hi - lo + TILE - 1) / TILE);
-    int incl = tiles;
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-      const int y = __shfl_up(incl, d);
-      if (lane >= d) incl += y;
-    }
-    const int total = __shfl(incl, WAVE - 1);
-    if (t < base + total) {
-      const bool mine = t >= base + incl - tiles && t < base + incl;
-      const unsigned long long vote = __ballot(mine);
-      const int src = __ffsll((long long)vote) - 1;
-      b = c + src;
-      const int first = __shfl(base + incl - tiles, src);
-      const int64_t plo = __shfl((long long)lo, src), phi = __shfl((long long)hi, src);
-      row0 = plo + (int64_t)(t - first) * TILE;
-      row_end = phi;
-      return true;
-    }
-    base += total;
-  }
-  return false;
-}
-
-// by value, selected with a workgroup-uniform index (see attn_kernels.hip: a reference into the argument segment turned
-// every pointer use inside the loop into a vector load)
-__device__ __forceinline__ Prob pick(const Args& a, int pi) { return pi ? a.p[1] : a.p[0]; }
-__device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 
 template <int H, int M>
 __global__ __launch_bounds__(TPB) void attn_node_scores_kernel(Args a) {
@@ -223,45 +173,39 @@ int launch_heads(int heads, unsigned grid, hipStream_t st, const Args& a) {
   return CGVP_ERR_UNSUPPORTED_DIMS;
 }
 
-int node_scores(const cgvp_attn_score_problem* probs, int32_t num_problems, int64_t num_pairs, int32_t heads, int M,
+int node_scores(const cgvp_attn_score_problem* probs, int32_t num_problems, int64_t num_pairs, int32_t heads, int head_dim,
                 float scale, void* stream) {
-  if (!probs || num_problems < 1 || num_problems > 2 || num_pairs < 0 || num_pairs >= ((int64_t)1 << 30) || heads < 1)
-    return CGVP_ERR_BAD_ARG;
-  if ((int64_t)heads * M > MAX_H) return CGVP_ERR_UNSUPPORTED_DIMS;
-  const int HD = TILE * M;
-  Args a;
-  a.nprob = num_problems; a.B = (int)num_pairs; a.scale = scale;
-  // the problem whose key tiles walk the most queries gets the low workgroup indices (they start first), as the
-  // d K / d V launch of cgvp_attn_bwd orders its two
-  const bool swap = num_problems == 2 && probs[1].num_q > probs[0].num_q;
-  const uintptr_t lse_align = heads % 4 == 0 ? 15 : 3;
-  for (int i = 0; i < 2; ++i) {
-    Prob& p = a.p[i];
-    p = Prob{};
-    if (i >= num_problems) continue;
-    const cgvp_attn_score_problem& s = probs[swap ? 1 - i : i];
-    if (s.num_q < 0 || s.num_k < 0 || !s.q_ptr || !s.k_ptr) return CGVP_ERR_BAD_ARG;
-    if ((s.num_q + TILE) * (int64_t)(heads * HD) >= ((int64_t)1 << 31) || (s.num_k + TILE) * (int64_t)(heads * HD) >= ((int64_t)1 << 31))
-      return CGVP_ERR_BAD_ARG;                             // the kernel addresses rows with 32-bit element offsets
-    if (s.num_q > 0 && (!s.q || !s.lse)) return CGVP_ERR_BAD_ARG;
-    if (s.num_k > 0 && (!s.k || !s.out_mean || !s.out_max)) return CGVP_ERR_BAD_ARG;
-    if (((uintptr_t)s.q & 15) || ((uintptr_t)s.k & 15) || ((uintptr_t)s.lse & lse_align)) return CGVP_ERR_BAD_ARG;
-    if ((((uintptr_t)s.out_mean | (uintptr_t)s.out_max) & 3) || (((uintptr_t)s.q_ptr | (uintptr_t)s.k_ptr) & 7)) return CGVP_ERR_BAD_ARG;
-    p.q = s.q; p.k = s.k; p.lse = s.lse; p.q_ptr = s.q_ptr; p.k_ptr = s.k_ptr;
-    p.out_mean = s.out_mean; p.out_max = s.out_max;
-    p.units = (int32_t)((s.num_k + TILE - 1) / TILE + num_pairs);
-  }
-  if (num_pairs == 0) return 0;
-  const unsigned grid = (unsigned)((int64_t)a.p[0].units + a.p[1].units);
-  hipStream_t st = (hipStream_t)stream;
-  int rc = 0;
-  switch (M) {
-    case 1: rc = launch_heads<1>(heads, grid, st, a); break;
-    case 2: rc = launch_heads<2>(heads, grid, st, a); break;
-    default: rc = launch_heads<4>(heads, grid, st, a); break;
-  }
-  if (rc) return rc;
-  return launch_status();
+  return with_m(head_dim, [&](auto m) -> int {
+    constexpr int M = decltype(m)::value;
+    if (!probs || num_problems < 1 || num_problems > 2 || num_pairs < 0 || num_pairs >= ((int64_t)1 << 30) || heads < 1)
+      return CGVP_ERR_BAD_ARG;
+    if ((int64_t)heads * M > MAX_H) return CGVP_ERR_UNSUPPORTED_DIMS;
+    const int64_t E = (int64_t)heads * TILE * M;
+    Args a;
+    a.nprob = num_problems; a.B = (int)num_pairs; a.scale = scale;
+    // the problem whose key tiles walk the most queries gets the low workgroup indices (they start first), as the
+    // d K / d V launch of cgvp_attn_bwd orders its two
+    const bool swap = num_problems == 2 && probs[1].num_q > probs[0].num_q;
+    for (int i = 0; i < 2; ++i) {
+      Prob& p = a.p[i];
+      p = Prob{};
+      if (i >= num_problems) continue;
+      const cgvp_attn_score_problem& s = probs[swap ? 1 - i : i];
+      if (!side_ok(s.num_q, s.q_ptr, E) || !side_ok(s.num_k, s.k_ptr, E)) return CGVP_ERR_BAD_ARG;
+      if (s.num_q > 0 && (!s.q || !s.lse)) return CGVP_ERR_BAD_ARG;
+      if (s.num_k > 0 && (!s.k || !s.out_mean || !s.out_max)) return CGVP_ERR_BAD_ARG;
+      if (!aligned(16, s.q, s.k) || !aligned(heads % 4 == 0 ? 16 : 4, s.lse) || !aligned(4, s.out_mean, s.out_max) ||
+          !aligned(8, s.q_ptr, s.k_ptr))
+        return CGVP_ERR_BAD_ARG;
+      p.q = s.q; p.k = s.k; p.lse = s.lse; p.q_ptr = s.q_ptr; p.k_ptr = s.k_ptr;
+      p.out_mean = s.out_mean; p.out_max = s.out_max;
+      p.units = (int32_t)((s.num_k + TILE - 1) / TILE + num_pairs);
+    }
+    if (num_pairs == 0) return 0;
+    const unsigned grid = (unsigned)((int64_t)a.p[0].units + a.p[1].units);
+    if (int rc = launch_heads<M>(heads, grid, (hipStream_t)stream, a)) return rc;
+    return launch_status();
+  });
 }
 
 }  // namespace
@@ -270,12 +214,11 @@ extern "C" int cgvp_attn_score_version(void) { return CGVP_ATTN_SCORE_VERSION; }
 
 extern "C" int cgvp_attn_node_scores(const cgvp_attn_score_problem* probs, int32_t num_problems, int64_t num_pairs,
                                      int32_t heads, float scale, void* stream) {
-  return node_scores(probs, num_problems, num_pairs, heads, 1, scale, stream);
+  return node_scores(probs, num_problems, num_pairs, heads, 16, scale, stream);
 }
 
 // ---- include/caster_gvp_attnhd.h
 extern "C" int cgvp_attn_node_scores_hd(const cgvp_attn_score_problem* probs, int32_t num_problems, int64_t num_pairs,
                                         int32_t heads, int32_t head_dim, float scale, void* stream) {
-  if (head_dim != 16 && head_dim != 32 && head_dim != 64) return CGVP_ERR_UNSUPPORTED_DIMS;
-  return node_scores(probs, num_problems, num_pairs, heads, head_dim / 16, scale, stream);
+  return node_scores(probs, num_problems, num_pairs, heads, head_dim, scale, stream);
 }

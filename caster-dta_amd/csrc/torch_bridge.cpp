@@ -762,16 +762,15 @@ struct FastLinear : public Function<FastLinear> {
 
 // The varlen cross-attention core, both directions in one launch (gvp_hip/attention_ops.py caster_gvp::cross_attention)
 struct CrossAttention : public Function<CrossAttention> {
-  static void fill(cgvp_attn_problem* P, const at::Tensor& q_r, const at::Tensor& k_a, const at::Tensor& v_a, const at::Tensor& q_a,
-                   const at::Tensor& k_r, const at::Tensor& v_r, const at::Tensor& rptr, const at::Tensor& aptr) {
-    P[0] = cgvp_attn_problem{};
-    P[1] = cgvp_attn_problem{};
-    P[0].q = (const float*)q_r.data_ptr(); P[0].k = (const float*)k_a.data_ptr(); P[0].v = (const float*)v_a.data_ptr();
-    P[0].q_ptr = (const int64_t*)rptr.data_ptr(); P[0].k_ptr = (const int64_t*)aptr.data_ptr();
-    P[0].num_q = q_r.size(0); P[0].num_k = k_a.size(0);
-    P[1].q = (const float*)q_a.data_ptr(); P[1].k = (const float*)k_r.data_ptr(); P[1].v = (const float*)v_r.data_ptr();
-    P[1].q_ptr = (const int64_t*)aptr.data_ptr(); P[1].k_ptr = (const int64_t*)rptr.data_ptr();
-    P[1].num_q = q_a.size(0); P[1].num_k = k_r.size(0);
+  // `t`: q_r, k_a, v_a, q_a, k_r, v_r -- direction i takes t[3i .. 3i + 2], its queries' offsets and then its keys'
+  static void fill(cgvp_attn_problem* P, const at::Tensor* t, const at::Tensor& rptr, const at::Tensor& aptr) {
+    const at::Tensor* ptrs[2] = {&rptr, &aptr};
+    for (int i = 0; i < 2; ++i) {
+      P[i] = cgvp_attn_problem{};
+      P[i].q = (const float*)t[3 * i].data_ptr(); P[i].k = (const float*)t[3 * i + 1].data_ptr(); P[i].v = (const float*)t[3 * i + 2].data_ptr();
+      P[i].q_ptr = (const int64_t*)ptrs[i]->data_ptr(); P[i].k_ptr = (const int64_t*)ptrs[1 - i]->data_ptr();
+      P[i].num_q = t[3 * i].size(0); P[i].num_k = t[3 * i + 1].size(0);
+    }
   }
   // Both directions in ONE launch when their head dims agree, else one launch each on the same stream; scale = 1 / sqrt(head_dim)
   template <class Fn>
@@ -807,7 +806,7 @@ struct CrossAttention : public Function<CrossAttention> {
     at::Tensor o_r = at::empty({N, E_r}, t[0].options()), o_a = at::empty({Na, E_a}, t[0].options());
     at::Tensor lse_r = at::empty({N, heads}, t[0].options()), lse_a = at::empty({Na, heads}, t[0].options());
     cgvp_attn_problem P[2];
-    fill(P, t[0], t[1], t[2], t[3], t[4], t[5], rptr, aptr);
+    fill(P, t, rptr, aptr);
     P[0].out = (float*)ptr(o_r); P[0].lse = (float*)ptr(lse_r);
     P[1].out = (float*)ptr(o_a); P[1].lse = (float*)ptr(lse_a);
     launch(cgvp_attn_fwd_hd, "cgvp_attn_fwd_hd", P, B, heads, hd, current_stream(t[0]));
@@ -826,13 +825,13 @@ struct CrossAttention : public Function<CrossAttention> {
     at::Tensor g_o_a = go[1].defined() ? rows_f32(go[1], "d o_a") : at::zeros_like(sv[7]);
     at::Tensor outs[6];
     for (int i = 0; i < 6; ++i) outs[i] = at::empty_like(sv[i]);
-    at::Tensor d_r = at::empty_like(sv[8]), d_a = at::empty_like(sv[9]);
+    const at::Tensor g_o[2] = {g_o_r, g_o_a}, delta[2] = {at::empty_like(sv[8]), at::empty_like(sv[9])};
     cgvp_attn_problem P[2];
-    fill(P, sv[0], sv[1], sv[2], sv[3], sv[4], sv[5], sv[10], sv[11]);
-    P[0].out = (float*)ptr(sv[6]); P[0].lse = (float*)ptr(sv[8]); P[0].g_out = (const float*)ptr(g_o_r); P[0].delta = (float*)ptr(d_r);
-    P[0].g_q = (float*)ptr(outs[0]); P[0].g_k = (float*)ptr(outs[1]); P[0].g_v = (float*)ptr(outs[2]);
-    P[1].out = (float*)ptr(sv[7]); P[1].lse = (float*)ptr(sv[9]); P[1].g_out = (const float*)ptr(g_o_a); P[1].delta = (float*)ptr(d_a);
-    P[1].g_q = (float*)ptr(outs[3]); P[1].g_k = (float*)ptr(outs[4]); P[1].g_v = (float*)ptr(outs[5]);
+    fill(P, sv.data(), sv[10], sv[11]);
+    for (int i = 0; i < 2; ++i) {                                   // saved: ..., o_r, o_a, lse_r, lse_a, ...
+      P[i].out = (float*)ptr(sv[6 + i]); P[i].lse = (float*)ptr(sv[8 + i]); P[i].g_out = (const float*)ptr(g_o[i]); P[i].delta = (float*)ptr(delta[i]);
+      P[i].g_q = (float*)ptr(outs[3 * i]); P[i].g_k = (float*)ptr(outs[3 * i + 1]); P[i].g_v = (float*)ptr(outs[3 * i + 2]);
+    }
     launch(cgvp_attn_bwd_hd, "cgvp_attn_bwd_hd", P, sv[10].numel() - 1, heads, hd, current_stream(sv[0]));
     // the two directions share no operand: a residue-side tensor gets its gradient from exactly one of them
     return {outs[0], outs[1], outs[2], outs[3], outs[4], outs[5], at::Tensor(), at::Tensor(), at::Tensor()};

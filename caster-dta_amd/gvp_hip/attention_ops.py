@@ -78,19 +78,25 @@ def head_dim_of(t, name, heads):
     return hd
 
 
+def _check_rows(r0, r1, r2, a0, a1, a2, rptr, aptr):
+    """What every attention op asks of its row counts: the three residue-side tensors agree, the three atom-side tensors
+    agree, and rptr / aptr are both [num_pairs + 1].  (gvp_hip.attention_scores uses it too.)"""
+    if not (r0.shape[0] == r1.shape[0] == r2.shape[0] and a0.shape[0] == a1.shape[0] == a2.shape[0]):
+        raise ValueError("row counts of the residue / atom tensors disagree")
+    if rptr.shape != aptr.shape or rptr.dim() != 1 or rptr.numel() < 1:
+        raise ValueError("rptr / aptr must both be [num_pairs + 1]")
+
+
 def _check(q_r, k_a, v_a, q_a, k_r, v_r, rptr, aptr, heads):
-    """The check of the shipped head shape alone: every operand is [rows, 16 * heads].  No op calls it any more (they take
-    `_check_hd`); it is kept because tests/test_attention_edges.py holds it to its refusals, one of which (4 heads at
-    width 128) is a shape `_check_hd` accepts.  It can go when that test may change."""
+    """The width rule of the shipped head shape alone: every operand is [rows, 16 * heads].  No op calls it (they take
+    `_check_hd`); tests/test_attention_edges.py holds it to its refusals, one of which (4 heads at width 128) is a shape
+    `_check_hd` accepts."""
     E = heads * HEAD_DIM
     for name, t in (("q_r", q_r), ("k_a", k_a), ("v_a", v_a), ("q_a", q_a), ("k_r", k_r), ("v_r", v_r)):
         if t.dim() != 2 or t.shape[1] != E:
             raise NotImplementedError(f"{name}: the attention kernels are compiled for head_dim 16 "
                                       f"(embed = 16 * heads = {E}), got {tuple(t.shape)}")
-    if not (q_r.shape[0] == k_r.shape[0] == v_r.shape[0] and q_a.shape[0] == k_a.shape[0] == v_a.shape[0]):
-        raise ValueError("row counts of the residue / atom tensors disagree")
-    if rptr.shape != aptr.shape or rptr.dim() != 1 or rptr.numel() < 1:
-        raise ValueError("rptr / aptr must both be [num_pairs + 1]")
+    _check_rows(q_r, k_r, v_r, q_a, k_a, v_a, rptr, aptr)
 
 
 def _check_hd(q_r, k_a, v_a, q_a, k_r, v_r, rptr, aptr, heads):
@@ -102,109 +108,38 @@ def _check_hd(q_r, k_a, v_a, q_a, k_r, v_r, rptr, aptr, heads):
             if t.dim() != 2 or t.shape[1] != q.shape[1]:
                 raise NotImplementedError(f"{name}: keys and values have the width of their queries "
                                           f"({qn}: {q.shape[1]} = {heads} heads x head_dim {hds[-1]}), got {tuple(t.shape)}")
-    if not (q_r.shape[0] == k_r.shape[0] == v_r.shape[0] and q_a.shape[0] == k_a.shape[0] == v_a.shape[0]):
-        raise ValueError("row counts of the residue / atom tensors disagree")
-    if rptr.shape != aptr.shape or rptr.dim() != 1 or rptr.numel() < 1:
-        raise ValueError("rptr / aptr must both be [num_pairs + 1]")
+    _check_rows(q_r, k_r, v_r, q_a, k_a, v_a, rptr, aptr)
     return tuple(hds)
 
 
+def launch_plan(hds):
+    """(first problem, number of problems, head_dim, scale = 1 / sqrt(head_dim)) of every launch of an entry point of
+    caster_gvp_attnhd.h on both directions: ONE launch with two problems when their head dims agree, else one launch with
+    one problem each, on the same stream."""
+    if hds[0] == hds[1]:
+        return ((0, 2, hds[0], 1.0 / math.sqrt(hds[0])),)
+    return ((0, 1, hds[0], 1.0 / math.sqrt(hds[0])), (1, 1, hds[1], 1.0 / math.sqrt(hds[1])))
+
+
 def _launch(name, P, B, heads, hds, R=None):
-    """The entry point `name` of caster_gvp_attnhd.h on both directions: ONE launch with two problems when their head
-    dims agree, else one launch with one problem each, on the same stream.  scale = 1 / sqrt(head_dim)."""
     fn = getattr(hd_lib(), name)
-    for first, n in (((0, 2),) if hds[0] == hds[1] else ((0, 1), (1, 1))):
-        args = [C.pointer(P[first]), n, B, heads, hds[first], 1.0 / math.sqrt(hds[first])]
+    for first, n, hd, scale in launch_plan(hds):
+        args = [C.pointer(P[first]), n, B, heads, hd, scale]
         if name != "cgvp_attn_weights_hd":
             args.append(None if R is None else C.pointer(R[first]))
         _lib.check(fn(*args, _stream()), name)
 
 
-@torch.library.custom_op("caster_gvp::cross_attention", mutates_args=(), device_types="cuda")
-def cross_attention_op(q_r: Tensor, k_a: Tensor, v_a: Tensor, q_a: Tensor, k_r: Tensor, v_r: Tensor, rptr: Tensor,
-                       aptr: Tensor, heads: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
-    """-> (o_r [N, E], o_a [Na, E], lse_r [N, heads], lse_a [Na, heads])."""
-    hds = _check_hd(q_r, k_a, v_a, q_a, k_r, v_r, rptr, aptr, heads)
-    ts = [_f32(t, "attention operand") for t in (q_r, k_a, v_a, q_a, k_r, v_r)]
-    rptr, aptr = _i64c(rptr, "rptr"), _i64c(aptr, "aptr")
-    dev = ts[0].device
-    N, Na, B = int(q_r.shape[0]), int(q_a.shape[0]), int(rptr.numel()) - 1
-    f32 = dict(dtype=torch.float32, device=dev)
-    o_r, o_a = torch.empty(N, heads * hds[0], **f32), torch.empty(Na, heads * hds[1], **f32)
-    lse_r, lse_a = torch.empty(N, heads, **f32), torch.empty(Na, heads, **f32)
-    P = _problems(*ts, rptr, aptr)
-    P[0].out, P[0].lse, P[1].out, P[1].lse = _ptr(o_r).value or 0, _ptr(lse_r).value or 0, _ptr(o_a).value or 0, _ptr(lse_a).value or 0
-    with torch.cuda.device(dev):
-        _launch("cgvp_attn_fwd_hd", P, B, heads, hds)
-    return o_r, o_a, lse_r, lse_a
-
-
-@cross_attention_op.register_fake
-def _(q_r, k_a, v_a, q_a, k_r, v_r, rptr, aptr, heads):
-    f = lambda t, *s: t.new_empty(s, dtype=torch.float32)
-    return (f(q_r, q_r.shape[0], q_r.shape[1]), f(q_a, q_a.shape[0], q_a.shape[1]), f(q_r, q_r.shape[0], heads),
-            f(q_a, q_a.shape[0], heads))
-
-
-@torch.library.custom_op("caster_gvp::cross_attention_backward", mutates_args=(), device_types="cuda")
-def cross_attention_backward_op(g_o_r: Tensor, g_o_a: Tensor, q_r: Tensor, k_a: Tensor, v_a: Tensor, q_a: Tensor,
-                                k_r: Tensor, v_r: Tensor, o_r: Tensor, o_a: Tensor, lse_r: Tensor, lse_a: Tensor,
-                                rptr: Tensor, aptr: Tensor,
-                                heads: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
-    """-> (g_q_r, g_k_a, g_v_a, g_q_a, g_k_r, g_v_r)."""
-    hds = (head_dim_of(q_r, "q_r", heads), head_dim_of(q_a, "q_a", heads))      # (the forward checked the rest)
-    ts = [_f32(t, "attention operand") for t in (q_r, k_a, v_a, q_a, k_r, v_r)]
-    g_o_r, g_o_a, o_r, o_a = (_f32(t, "attention gradient") for t in (g_o_r, g_o_a, o_r, o_a))
-    lse_r, lse_a = _f32(lse_r, "lse"), _f32(lse_a, "lse")
-    rptr, aptr = _i64c(rptr, "rptr"), _i64c(aptr, "aptr")
-    dev = ts[0].device
-    B = int(rptr.numel()) - 1
-    outs = [torch.empty_like(t) for t in ts]                 # g_q_r, g_k_a, g_v_a, g_q_a, g_k_r, g_v_r
-    d_r, d_a = torch.empty_like(lse_r), torch.empty_like(lse_a)
-    P = _problems(*ts, rptr, aptr)
-    v = lambda t: _ptr(t).value or 0
-    P[0].out, P[0].lse, P[0].g_out, P[0].delta = v(o_r), v(lse_r), v(g_o_r), v(d_r)
-    P[0].g_q, P[0].g_k, P[0].g_v = v(outs[0]), v(outs[1]), v(outs[2])
-    P[1].out, P[1].lse, P[1].g_out, P[1].delta = v(o_a), v(lse_a), v(g_o_a), v(d_a)
-    P[1].g_q, P[1].g_k, P[1].g_v = v(outs[3]), v(outs[4]), v(outs[5])
-    with torch.cuda.device(dev):
-        _launch("cgvp_attn_bwd_hd", P, B, heads, hds)
-    return tuple(outs)
-
-
-@cross_attention_backward_op.register_fake
-def _(g_o_r, g_o_a, q_r, k_a, v_a, q_a, k_r, v_r, o_r, o_a, lse_r, lse_a, rptr, aptr, heads):
-    return tuple(t.new_empty(t.shape, dtype=torch.float32) for t in (q_r, k_a, v_a, q_a, k_r, v_r))
-
-
-def _attn_setup(ctx, inputs, output):
-    q_r, k_a, v_a, q_a, k_r, v_r, rptr, aptr, heads = inputs
-    o_r, o_a, lse_r, lse_a = output
-    ctx.heads = heads
-    ctx.set_materialize_grads(False)          # the log-sum-exp outputs never carry a gradient: no zero fills for them
-    ctx.save_for_backward(q_r, k_a, v_a, q_a, k_r, v_r, o_r, o_a, lse_r, lse_a, rptr, aptr)
-
-
-def _attn_backward(ctx, g_o_r, g_o_a, g_lse_r, g_lse_a):
-    q_r, k_a, v_a, q_a, k_r, v_r, o_r, o_a, lse_r, lse_a, rptr, aptr = ctx.saved_tensors
-    if g_o_r is None and g_o_a is None:
-        return (None,) * 9
-    g_o_r = torch.zeros_like(o_r) if g_o_r is None else g_o_r
-    g_o_a = torch.zeros_like(o_a) if g_o_a is None else g_o_a
-    grads = torch.ops.caster_gvp.cross_attention_backward(g_o_r.contiguous(), g_o_a.contiguous(), q_r, k_a, v_a, q_a,
-                                                          k_r, v_r, o_r, o_a, lse_r, lse_a, rptr, aptr, ctx.heads)
-    # the two directions share no operand: a residue-side tensor gets its gradient from exactly one of them
-    return (*grads, None, None, None)
-
-
-torch.library.register_autograd("caster_gvp::cross_attention", _attn_backward, setup_context=_attn_setup)
-torch.library.register_autocast("caster_gvp::cross_attention", "cuda", torch.float32)
+def _addr(t):
+    return _ptr(t).value or 0
 
 
 # ------------------------------------------------------------------------------------------------ attention dropout
 # include/caster_gvp_attndrop.h: the same kernels with nn.MultiheadAttention's training-mode dropout on the softmax
 # probabilities, factors regenerated in the kernels from the step's {seed, offset} pair -- a header, a version and a
-# signature table of their own, bound on the handle of `_lib.lib()`.
+# signature table of their own, bound on the handle of `_lib.lib()`.  The ops below go through the _hd entry points,
+# where a NULL generator is "no dropout": `cross_attention` and `cross_attention_dropout` share one body, the second
+# with the trailing arguments `drop` = (pair, site_r, site_a, p_r, p_a).
 ATTN_DROPOUT_VERSION = 1     # CGVP_ATTN_DROPOUT_VERSION
 DROPOUT_MAX_HEADS = 128      # CGVP_ATTN_DROPOUT_MAX_HEADS
 
@@ -237,13 +172,7 @@ def _rngs(pair, site_r, site_a, p_r, p_a):
     return R
 
 
-@torch.library.custom_op("caster_gvp::cross_attention_dropout", mutates_args=(), device_types="cuda")
-def cross_attention_dropout_op(q_r: Tensor, k_a: Tensor, v_a: Tensor, q_a: Tensor, k_r: Tensor, v_r: Tensor, rptr: Tensor,
-                               aptr: Tensor, heads: int, pair: Tensor, site_r: int, site_a: int, p_r: float,
-                               p_a: float) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
-    """`cross_attention` with dropout on the softmax probabilities (nn.MultiheadAttention in training mode):
-    o = (softmax(q k^T / sqrt(head_dim)) o f) v, f in {0, 1/(1-p)} a pure function of (pair, site, head, query row, key row).
-    -> (o_r, o_a, lse_r, lse_a); the lse are those of the UNdropped scores.  p_r = p_a = 0 is `cross_attention`."""
+def _forward(q_r, k_a, v_a, q_a, k_r, v_r, rptr, aptr, heads, *drop):
     hds = _check_hd(q_r, k_a, v_a, q_a, k_r, v_r, rptr, aptr, heads)
     ts = [_f32(t, "attention operand") for t in (q_r, k_a, v_a, q_a, k_r, v_r)]
     rptr, aptr = _i64c(rptr, "rptr"), _i64c(aptr, "aptr")
@@ -253,26 +182,15 @@ def cross_attention_dropout_op(q_r: Tensor, k_a: Tensor, v_a: Tensor, q_a: Tenso
     o_r, o_a = torch.empty(N, heads * hds[0], **f32), torch.empty(Na, heads * hds[1], **f32)
     lse_r, lse_a = torch.empty(N, heads, **f32), torch.empty(Na, heads, **f32)
     P = _problems(*ts, rptr, aptr)
-    P[0].out, P[0].lse, P[1].out, P[1].lse = _ptr(o_r).value or 0, _ptr(lse_r).value or 0, _ptr(o_a).value or 0, _ptr(lse_a).value or 0
-    R = _rngs(pair, site_r, site_a, p_r, p_a)
+    for p, o, lse in zip(P, (o_r, o_a), (lse_r, lse_a)):
+        p.out, p.lse = _addr(o), _addr(lse)
+    R = _rngs(*drop) if drop else None
     with torch.cuda.device(dev):
         _launch("cgvp_attn_fwd_hd", P, B, heads, hds, R)
     return o_r, o_a, lse_r, lse_a
 
 
-@cross_attention_dropout_op.register_fake
-def _(q_r, k_a, v_a, q_a, k_r, v_r, rptr, aptr, heads, pair, site_r, site_a, p_r, p_a):
-    f = lambda t, *s: t.new_empty(s, dtype=torch.float32)
-    return (f(q_r, q_r.shape[0], q_r.shape[1]), f(q_a, q_a.shape[0], q_a.shape[1]), f(q_r, q_r.shape[0], heads),
-            f(q_a, q_a.shape[0], heads))
-
-
-@torch.library.custom_op("caster_gvp::cross_attention_dropout_backward", mutates_args=(), device_types="cuda")
-def cross_attention_dropout_backward_op(g_o_r: Tensor, g_o_a: Tensor, q_r: Tensor, k_a: Tensor, v_a: Tensor, q_a: Tensor,
-                                        k_r: Tensor, v_r: Tensor, o_r: Tensor, o_a: Tensor, lse_r: Tensor, lse_a: Tensor,
-                                        rptr: Tensor, aptr: Tensor, heads: int, pair: Tensor, site_r: int, site_a: int,
-                                        p_r: float, p_a: float) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
-    """-> (g_q_r, g_k_a, g_v_a, g_q_a, g_k_r, g_v_r); `pair`, sites and p are the forward's: the factors are regenerated."""
+def _backward(g_o_r, g_o_a, q_r, k_a, v_a, q_a, k_r, v_r, o_r, o_a, lse_r, lse_a, rptr, aptr, heads, *drop):
     hds = (head_dim_of(q_r, "q_r", heads), head_dim_of(q_a, "q_a", heads))      # (the forward checked the rest)
     ts = [_f32(t, "attention operand") for t in (q_r, k_a, v_a, q_a, k_r, v_r)]
     g_o_r, g_o_a, o_r, o_a = (_f32(t, "attention gradient") for t in (g_o_r, g_o_a, o_r, o_a))
@@ -283,44 +201,88 @@ def cross_attention_dropout_backward_op(g_o_r: Tensor, g_o_a: Tensor, q_r: Tenso
     outs = [torch.empty_like(t) for t in ts]                 # g_q_r, g_k_a, g_v_a, g_q_a, g_k_r, g_v_r
     d_r, d_a = torch.empty_like(lse_r), torch.empty_like(lse_a)
     P = _problems(*ts, rptr, aptr)
-    v = lambda t: _ptr(t).value or 0
-    P[0].out, P[0].lse, P[0].g_out, P[0].delta = v(o_r), v(lse_r), v(g_o_r), v(d_r)
-    P[0].g_q, P[0].g_k, P[0].g_v = v(outs[0]), v(outs[1]), v(outs[2])
-    P[1].out, P[1].lse, P[1].g_out, P[1].delta = v(o_a), v(lse_a), v(g_o_a), v(d_a)
-    P[1].g_q, P[1].g_k, P[1].g_v = v(outs[3]), v(outs[4]), v(outs[5])
-    R = _rngs(pair, site_r, site_a, p_r, p_a)
+    for i, (p, o, lse, g_o, d) in enumerate(zip(P, (o_r, o_a), (lse_r, lse_a), (g_o_r, g_o_a), (d_r, d_a))):
+        p.out, p.lse, p.g_out, p.delta = _addr(o), _addr(lse), _addr(g_o), _addr(d)
+        p.g_q, p.g_k, p.g_v = _addr(outs[3 * i]), _addr(outs[3 * i + 1]), _addr(outs[3 * i + 2])
+    R = _rngs(*drop) if drop else None
     with torch.cuda.device(dev):
         _launch("cgvp_attn_bwd_hd", P, B, heads, hds, R)
     return tuple(outs)
 
 
-@cross_attention_dropout_backward_op.register_fake
-def _(g_o_r, g_o_a, q_r, k_a, v_a, q_a, k_r, v_r, o_r, o_a, lse_r, lse_a, rptr, aptr, heads, pair, site_r, site_a, p_r, p_a):
+def _fake_forward(q_r, k_a, v_a, q_a, k_r, v_r, rptr, aptr, heads, *drop):
+    f = lambda t, *s: t.new_empty(s, dtype=torch.float32)
+    return (f(q_r, q_r.shape[0], q_r.shape[1]), f(q_a, q_a.shape[0], q_a.shape[1]), f(q_r, q_r.shape[0], heads),
+            f(q_a, q_a.shape[0], heads))
+
+
+def _fake_backward(g_o_r, g_o_a, q_r, k_a, v_a, q_a, k_r, v_r, *rest):
     return tuple(t.new_empty(t.shape, dtype=torch.float32) for t in (q_r, k_a, v_a, q_a, k_r, v_r))
 
 
-def _drop_setup(ctx, inputs, output):
-    q_r, k_a, v_a, q_a, k_r, v_r, rptr, aptr, heads, pair, site_r, site_a, p_r, p_a = inputs
-    o_r, o_a, lse_r, lse_a = output
-    ctx.heads, ctx.sites, ctx.ps = heads, (site_r, site_a), (p_r, p_a)
-    ctx.set_materialize_grads(False)          # the log-sum-exp outputs never carry a gradient, as in _attn_setup
-    ctx.save_for_backward(q_r, k_a, v_a, q_a, k_r, v_r, o_r, o_a, lse_r, lse_a, rptr, aptr, pair)
+@torch.library.custom_op("caster_gvp::cross_attention", mutates_args=(), device_types="cuda")
+def cross_attention_op(q_r: Tensor, k_a: Tensor, v_a: Tensor, q_a: Tensor, k_r: Tensor, v_r: Tensor, rptr: Tensor,
+                       aptr: Tensor, heads: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """-> (o_r [N, E], o_a [Na, E], lse_r [N, heads], lse_a [Na, heads])."""
+    return _forward(q_r, k_a, v_a, q_a, k_r, v_r, rptr, aptr, heads)
 
 
-def _drop_backward(ctx, g_o_r, g_o_a, g_lse_r, g_lse_a):
-    q_r, k_a, v_a, q_a, k_r, v_r, o_r, o_a, lse_r, lse_a, rptr, aptr, pair = ctx.saved_tensors
+@torch.library.custom_op("caster_gvp::cross_attention_backward", mutates_args=(), device_types="cuda")
+def cross_attention_backward_op(g_o_r: Tensor, g_o_a: Tensor, q_r: Tensor, k_a: Tensor, v_a: Tensor, q_a: Tensor,
+                                k_r: Tensor, v_r: Tensor, o_r: Tensor, o_a: Tensor, lse_r: Tensor, lse_a: Tensor,
+                                rptr: Tensor, aptr: Tensor,
+                                heads: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """-> (g_q_r, g_k_a, g_v_a, g_q_a, g_k_r, g_v_r)."""
+    return _backward(g_o_r, g_o_a, q_r, k_a, v_a, q_a, k_r, v_r, o_r, o_a, lse_r, lse_a, rptr, aptr, heads)
+
+
+@torch.library.custom_op("caster_gvp::cross_attention_dropout", mutates_args=(), device_types="cuda")
+def cross_attention_dropout_op(q_r: Tensor, k_a: Tensor, v_a: Tensor, q_a: Tensor, k_r: Tensor, v_r: Tensor, rptr: Tensor,
+                               aptr: Tensor, heads: int, pair: Tensor, site_r: int, site_a: int, p_r: float,
+                               p_a: float) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """`cross_attention` with dropout on the softmax probabilities (nn.MultiheadAttention in training mode):
+    o = (softmax(q k^T / sqrt(head_dim)) o f) v, f in {0, 1/(1-p)} a pure function of (pair, site, head, query row, key row).
+    -> (o_r, o_a, lse_r, lse_a); the lse are those of the UNdropped scores.  p_r = p_a = 0 is `cross_attention`."""
+    return _forward(q_r, k_a, v_a, q_a, k_r, v_r, rptr, aptr, heads, pair, site_r, site_a, p_r, p_a)
+
+
+@torch.library.custom_op("caster_gvp::cross_attention_dropout_backward", mutates_args=(), device_types="cuda")
+def cross_attention_dropout_backward_op(g_o_r: Tensor, g_o_a: Tensor, q_r: Tensor, k_a: Tensor, v_a: Tensor, q_a: Tensor,
+                                        k_r: Tensor, v_r: Tensor, o_r: Tensor, o_a: Tensor, lse_r: Tensor, lse_a: Tensor,
+                                        rptr: Tensor, aptr: Tensor, heads: int, pair: Tensor, site_r: int, site_a: int,
+                                        p_r: float, p_a: float) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """-> (g_q_r, g_k_a, g_v_a, g_q_a, g_k_r, g_v_r); `pair`, sites and p are the forward's: the factors are regenerated."""
+    return _backward(g_o_r, g_o_a, q_r, k_a, v_a, q_a, k_r, v_r, o_r, o_a, lse_r, lse_a, rptr, aptr, heads,
+                     pair, site_r, site_a, p_r, p_a)
+
+
+def _attn_setup(ctx, inputs, output):
+    """inputs: the six operands, rptr, aptr, heads[, pair, site_r, site_a, p_r, p_a]; output: (o_r, o_a, lse_r, lse_a)."""
+    ctx.heads, ctx.drop = inputs[8], inputs[10:]
+    ctx.set_materialize_grads(False)          # the log-sum-exp outputs never carry a gradient: no zero fills for them
+    ctx.save_for_backward(*inputs[:6], *output, *inputs[6:8], *inputs[9:10])
+
+
+def _attn_backward(ctx, g_o_r, g_o_a, g_lse_r, g_lse_a):
+    saved = ctx.saved_tensors                 # q_r, k_a, v_a, q_a, k_r, v_r, o_r, o_a, lse_r, lse_a, rptr, aptr[, pair]
+    nones = (None,) * (len(saved) - 9 + len(ctx.drop))          # rptr, aptr, heads[, pair, sites, ps]
     if g_o_r is None and g_o_a is None:
-        return (None,) * 14
-    g_o_r = torch.zeros_like(o_r) if g_o_r is None else g_o_r
-    g_o_a = torch.zeros_like(o_a) if g_o_a is None else g_o_a
-    grads = torch.ops.caster_gvp.cross_attention_dropout_backward(
-        g_o_r.contiguous(), g_o_a.contiguous(), q_r, k_a, v_a, q_a, k_r, v_r, o_r, o_a, lse_r, lse_a, rptr, aptr, ctx.heads,
-        pair, *ctx.sites, *ctx.ps)
-    return (*grads, *(None,) * 8)
+        return (None,) * 6 + nones
+    g_o_r = torch.zeros_like(saved[6]) if g_o_r is None else g_o_r
+    g_o_a = torch.zeros_like(saved[7]) if g_o_a is None else g_o_a
+    op = torch.ops.caster_gvp.cross_attention_dropout_backward if ctx.drop else torch.ops.caster_gvp.cross_attention_backward
+    grads = op(g_o_r.contiguous(), g_o_a.contiguous(), *saved[:12], ctx.heads, *saved[12:], *ctx.drop)
+    # the two directions share no operand: a residue-side tensor gets its gradient from exactly one of them
+    return (*grads, *nones)
 
 
-torch.library.register_autograd("caster_gvp::cross_attention_dropout", _drop_backward, setup_context=_drop_setup)
-torch.library.register_autocast("caster_gvp::cross_attention_dropout", "cuda", torch.float32)
+cross_attention_op.register_fake(_fake_forward)
+cross_attention_dropout_op.register_fake(_fake_forward)
+cross_attention_backward_op.register_fake(_fake_backward)
+cross_attention_dropout_backward_op.register_fake(_fake_backward)
+for _name in ("caster_gvp::cross_attention", "caster_gvp::cross_attention_dropout"):
+    torch.library.register_autograd(_name, _attn_backward, setup_context=_attn_setup)
+    torch.library.register_autocast(_name, "cuda", torch.float32)
 
 
 @torch.library.custom_op("caster_gvp::cross_attention_weights", mutates_args=(), device_types="cuda")
@@ -341,9 +303,8 @@ def cross_attention_weights_op(q_r: Tensor, k_a: Tensor, lse_r: Tensor, q_a: Ten
         return w_r, w_a
     dummy_r, dummy_a = torch.empty(1, device=dev), torch.empty(1, device=dev)    # `out` is not written by this entry point
     P = _problems(*ts, rptr, aptr)
-    v = lambda t: _ptr(t).value or 0
-    P[0].out, P[0].lse, P[0].weights, P[0].weights_lq, P[0].weights_lk = v(dummy_r), v(lse_r), v(w_r), r_max, a_max
-    P[1].out, P[1].lse, P[1].weights, P[1].weights_lq, P[1].weights_lk = v(dummy_a), v(lse_a), v(w_a), a_max, r_max
+    P[0].out, P[0].lse, P[0].weights, P[0].weights_lq, P[0].weights_lk = _addr(dummy_r), _addr(lse_r), _addr(w_r), r_max, a_max
+    P[1].out, P[1].lse, P[1].weights, P[1].weights_lq, P[1].weights_lk = _addr(dummy_a), _addr(lse_a), _addr(w_a), a_max, r_max
     with torch.cuda.device(dev):
         _launch("cgvp_attn_weights_hd", P, B, heads, hds)
     return w_r, w_a

@@ -15,14 +15,13 @@ from __future__ import annotations
 
 import ctypes as C
 import functools
-import math
 from typing import List, Tuple
 
 import torch
 from torch import Tensor
 
 from . import _lib, attention_ops
-from ._lib import _on_gpu, _ptr, _stream
+from ._lib import _on_gpu, _stream
 
 ATTN_SCORE_VERSION = 1   # CGVP_ATTN_SCORE_VERSION
 MAX_HEADS = 8            # CGVP_ATTN_SCORE_MAX_HEADS
@@ -84,11 +83,6 @@ def _width(q, name, heads):
     return heads * hd, hd
 
 
-def _offsets(t, name):
-    _on_gpu(t, name)
-    return t.to(torch.int64).contiguous()
-
-
 @torch.library.custom_op("caster_gvp::cross_attention_node_scores", mutates_args=(), device_types="cuda")
 def cross_attention_node_scores_op(q_r: Tensor, k_a: Tensor, lse_r: Tensor, q_a: Tensor, k_r: Tensor, lse_a: Tensor,
                                    rptr: Tensor, aptr: Tensor, heads: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
@@ -109,12 +103,9 @@ def cross_attention_node_scores_op(q_r: Tensor, k_a: Tensor, lse_r: Tensor, q_a:
     q_r, k_a = _rows(q_r, "q_r", E_r), _rows(k_a, "k_a", E_r)
     q_a, k_r = _rows(q_a, "q_a", E_a), _rows(k_r, "k_r", E_a)
     lse_r, lse_a = _rows(lse_r, "lse_r", heads), _rows(lse_a, "lse_a", heads)
+    attention_ops._check_rows(q_r, k_r, lse_r, q_a, k_a, lse_a, rptr, aptr)
+    rptr, aptr = attention_ops._i64c(rptr, "rptr"), attention_ops._i64c(aptr, "aptr")
     N, Na = int(q_r.shape[0]), int(q_a.shape[0])
-    if not (k_r.shape[0] == lse_r.shape[0] == N and k_a.shape[0] == lse_a.shape[0] == Na):
-        raise ValueError("row counts of the residue / atom tensors disagree")
-    if rptr.shape != aptr.shape or rptr.dim() != 1 or rptr.numel() < 1:
-        raise ValueError("rptr / aptr must both be [num_pairs + 1]")
-    rptr, aptr = _offsets(rptr, "rptr"), _offsets(aptr, "aptr")
     dev, B = q_r.device, int(rptr.numel()) - 1
     # every key row of a pair is written by the kernel: with ptr[-1] == the row count (what PyG batches deliver, and what
     # caster_gvp::cross_attention assumes for its own outputs) nothing stays undefined and nothing needs a fill
@@ -122,16 +113,15 @@ def cross_attention_node_scores_op(q_r: Tensor, k_a: Tensor, lse_r: Tensor, q_a:
     atom_mean, atom_max = torch.empty(Na, **f32), torch.empty(Na, **f32)
     res_mean, res_max = torch.empty(N, **f32), torch.empty(N, **f32)
     P = (ScoreProblem * 2)()
-    v = lambda t: _ptr(t).value or 0
+    v = attention_ops._addr
     for p, (q, k, lse, qp, kp, mean, mx) in zip(P, ((q_r, k_a, lse_r, rptr, aptr, atom_mean, atom_max),
                                                      (q_a, k_r, lse_a, aptr, rptr, res_mean, res_max))):
         p.q, p.k, p.lse, p.q_ptr, p.k_ptr = v(q), v(k), v(lse), qp.data_ptr(), kp.data_ptr()
         p.num_q, p.num_k, p.out_mean, p.out_max = int(q.shape[0]), int(k.shape[0]), v(mean), v(mx)
     fn = hd_lib().cgvp_attn_node_scores_hd
     with torch.cuda.device(dev):
-        # one launch for both directions when their head dims agree, else one each on the same stream
-        for first, n, hd in (((0, 2, hd_r),) if hd_r == hd_a else ((0, 1, hd_r), (1, 1, hd_a))):
-            _lib.check(fn(C.pointer(P[first]), n, B, heads, hd, 1.0 / math.sqrt(hd), _stream()), "cgvp_attn_node_scores_hd")
+        for first, n, hd, scale in attention_ops.launch_plan((hd_r, hd_a)):
+            _lib.check(fn(C.pointer(P[first]), n, B, heads, hd, scale, _stream()), "cgvp_attn_node_scores_hd")
     return atom_mean, atom_max, res_mean, res_max
 
 
