@@ -29,6 +29,7 @@ from functools import partial
 
 import contextlib
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -455,6 +456,152 @@ class JointGNN(nn.Module):
         finally:
             self.node_attention, self.attention_weights = saved[1], saved[2]
             self.train(saved[0])
+
+    # ------------------------------------------------------------ pair lists over unique graphs (inference)
+    @torch.no_grad()
+    def score_pairs(self, protein_graph_data, molecule_graph_data, pairs=None, max_rows=262144):
+        """Affinities [K, 1] of a LIST OF PAIRS drawn from P unique proteins and D unique molecules, each encoded once.
+
+        The two dicts are ordinary batches of the unique graphs (with `ptr`, or `batch` from which it is built); `pairs`
+        is [K, 2] (protein index, molecule index) -- a tensor, an array or a list -- or None for the full cross product in
+        protein-major order.  A screen of one target against a library is P = 1; a variant scan against a panel is the
+        product.  Everything that does not depend on the partner runs once per unique graph: both encoders, the residue /
+        atom stacks and, for the first cross-attention layer, the pre-attention LayerNorms and the Q / K / V projections.
+        The pairs are then worked through in chunks of at most `max_rows` per-pair rows (`gvp_hip.pair_scoring.plan_pairs`:
+        summed residue rows plus summed atom rows; a pair larger than the budget is a chunk of its own):
+        caster_gvp::cross_attention_pairs on the unique rows, out_proj, the residual stream on the caster_gvp::expand_rows
+        copy, later layers on the per-pair rows, pooling, affinity head.  Predictions come back in pair order.
+
+        Contract: eval mode under no_grad (the training flag is restored); `ptr` of both sides and `pairs` are read to the
+        host ONCE, the call's only synchronisation; an index outside 0 .. P-1 / 0 .. D-1 raises IndexError before anything
+        is launched.  NotImplementedError, never a dense fallback: CPU tensors, a head shape `varlen_supported` refuses,
+        `enable_pair_parallel`.  Attention weights and node scores are not produced; `attention_weights`,
+        `node_attention` and `last_node_attention` are left as they are."""
+        from gvp_hip import pair_scoring as ps
+        xs = [d.get("x", None) for d in (protein_graph_data, molecule_graph_data)]
+        xs = [x[0] if isinstance(x, (tuple, list)) else x for x in xs]
+        if not all(torch.is_tensor(x) and x.is_cuda for x in xs):
+            raise NotImplementedError("score_pairs runs on MI355X only: both graph dicts must hold CUDA tensors")
+        if self._pair_parallel:
+            raise NotImplementedError("score_pairs does not shard pairs over ranks (enable_pair_parallel is on)")
+        dev = xs[0].device
+        cam = self.cross_attn_module
+        if cam is not None and not cam.varlen_supported(xs[0]):
+            raise NotImplementedError("score_pairs needs head shapes the varlen attention kernels are compiled for "
+                                      "(head_dim 16, 32 or 64 in both directions, one head count)")
+        ptr1, ptr2 = (self._unique_ptr(d, x) for d, x in zip((protein_graph_data, molecule_graph_data), xs))
+        # the one host read: both ptr tables and, when it lives on the device, the pair list
+        on_dev = torch.is_tensor(pairs) and pairs.is_cuda
+        flat = torch.cat([ptr1, ptr2] + ([pairs.reshape(-1).to(torch.int64)] if on_dev else [])).cpu().numpy()
+        n1, n2 = ptr1.numel(), ptr2.numel()
+        len1, len2 = flat[1:n1] - flat[:n1 - 1], flat[n1 + 1:n1 + n2] - flat[n1:n1 + n2 - 1]
+        if on_dev:
+            pairs = flat[n1 + n2:].reshape(-1, 2)
+        elif torch.is_tensor(pairs):
+            pairs = pairs.numpy()
+        chunks = ps.plan_pairs(len1, len2, pairs, max_rows)          # IndexError here, before the first launch
+        was_training = self.training
+        self.eval()
+        try:
+            return self._score_chunks(protein_graph_data, molecule_graph_data, ptr1, ptr2, chunks, dev)
+        finally:
+            self.train(was_training)
+
+    @staticmethod
+    def _unique_ptr(data, x):
+        """int64 [G + 1] row offsets of a batch of unique graphs on the device: `ptr` of the dict, else from `batch`."""
+        ptr = data.get("ptr", None)
+        if ptr is None:
+            batch = data.get("batch", None)
+            if batch is None:
+                return torch.tensor([0, x.shape[0]], dtype=torch.long, device=x.device)
+            counts = torch.bincount(batch)           # (sizes its result from batch.max(): only taken without `ptr`)
+            ptr = torch.cat([counts.new_zeros(1), counts.cumsum(0)])
+        return ptr.to(device=x.device, dtype=torch.long)
+
+    def _pair_affinity(self, protein, molecule):
+        """The head after the pooling, in eval mode: post-pool norm, activation, the protein / molecule stacks, the pair
+        embedding and the affinity MLP.  protein [K, r_dim], molecule [K, a_dim] -> [K, 1]."""
+        protein, molecule = self._pooled_stack(protein, 1), self._pooled_stack(molecule, 2)
+        return self._embed_pairs(protein, molecule)
+
+    def _pooled_stack(self, pooled, side):
+        norm, lins, norms = ((self.protein_post_pool_norm if self.include_post_pool_layernorm else None,
+                              self.protein_lins, self.protein_norms) if side == 1 else
+                             (self.molecule_post_pool_norm if self.include_post_pool_layernorm else None,
+                              self.molecule_lins, self.molecule_norms))
+        if norm is not None:
+            pooled = norm(pooled)
+        return self._stack(self.dropout(self.activation(pooled)), lins, norms)
+
+    def _embed_pairs(self, protein, molecule):
+        z = self.dropout(self.activation(self.pm_embed_lin(torch.cat([protein, molecule], dim=-1))))
+        return self.output_layer(self._stack(z, self.out_fc_layers, self.out_fc_norms))
+
+    def _score_chunks(self, protein_graph_data, molecule_graph_data, ptr1, ptr2, chunks, dev):
+        from gvp_hip import pair_scoring as ps
+        from gvp_hip.head_ops import fast_layer_norm, fast_linear
+        hdt = self.output_layer.weight.dtype
+        if not chunks:
+            return torch.empty(0, 1, dtype=hdt, device=dev)
+        # ---- once per unique graph
+        residue = self.protein_gnn(**{k: v for k, v in protein_graph_data.items() if k != "ptr"})
+        atom = self.molecule_gnn(**{k: v for k, v in molecule_graph_data.items() if k != "ptr"})
+        if not torch.is_autocast_enabled():
+            residue, atom = residue.to(hdt), atom.to(hdt)
+        residue = self._stack(residue, self.residue_lins, self.residue_norms)
+        atom = self._stack(atom, self.atom_lins, self.atom_norms)
+        # one upload of every chunk's four tables; the slices of an int64 vector keep the 8-byte alignment
+        tables = [t for c in chunks for t in (c.g1, c.g2, c.optr1, c.optr2)]
+        packed = torch.from_numpy(np.concatenate(tables)).to(dev, non_blocking=False)
+        views = packed.split([int(t.shape[0]) for t in tables])
+        if self.cross_attn_module is None:
+            # nothing depends on the partner before the pair embedding: pool and stack the unique graphs, index per pair
+            b1 = torch.repeat_interleave(torch.arange(ptr1.numel() - 1, device=dev), ptr1[1:] - ptr1[:-1],
+                                         output_size=residue.shape[0])
+            b2 = torch.repeat_interleave(torch.arange(ptr2.numel() - 1, device=dev), ptr2[1:] - ptr2[:-1],
+                                         output_size=atom.shape[0])
+            protein = self._pooled_stack(self._pool_rows(residue, b1, ptr1), 1)
+            molecule = self._pooled_stack(self._pool_rows(atom, b2, ptr2), 2)
+            g1 = torch.cat([views[4 * i] for i in range(len(chunks))])
+            g2 = torch.cat([views[4 * i + 1] for i in range(len(chunks))])
+            return self._embed_pairs(protein.index_select(0, g1), molecule.index_select(0, g2))
+        layers = list(self.cross_attn_module.cross_attn_layers)
+        L0 = layers[0]
+        E1, E2 = L0.embed1_to_2.embed_dim, L0.embed2_to_1.embed_dim
+        p12, p21 = L0._proj_parts(L0.embed1_to_2), L0._proj_parts(L0.embed2_to_1)
+        n1 = fast_layer_norm(residue, L0.preattn_norm1)
+        q1 = L0._q(p12, n1)
+        k2, v2 = L0._kv(p21, n1, E2)
+        n2 = fast_layer_norm(atom, L0.preattn_norm2)
+        q2 = L0._q(p21, n2)
+        k1, v1 = L0._kv(p12, n2, E1)
+        heads = L0.embed1_to_2.num_heads
+
+        def ff(seq, t):              # nn.Sequential(Linear, ReLU, Dropout, Linear) in eval mode
+            return fast_linear(seq[1](fast_linear(t, seq[0].weight, seq[0].bias)), seq[3].weight, seq[3].bias)
+
+        out = []
+        # ---- per chunk: only what depends on the partner
+        for i, c in enumerate(chunks):
+            g1, g2, optr1, optr2 = views[4 * i:4 * i + 4]
+            o1, o2 = ps.cross_attention_pairs(q1, k1, v1, q2, k2, v2, ptr1, ptr2, g1, g2, optr1, optr2, heads,
+                                              c.rows1, c.rows2)
+            a1 = fast_linear(o1, L0.embed1_to_2.out_proj.weight, L0.embed1_to_2.out_proj.bias)
+            a2 = fast_linear(o2, L0.embed2_to_1.out_proj.weight, L0.embed2_to_1.out_proj.bias)
+            e1, b1 = ps.expand_rows(residue, ptr1, g1, optr1, c.rows1)      # the residual stream; b: the pooling's batch
+            e2, b2 = ps.expand_rows(atom, ptr2, g2, optr2, c.rows2)
+            if L0.include_residual_stream:
+                e1 = e1 + a1
+                e1 = e1 + ff(L0.ff1, fast_layer_norm(e1, L0.ff_norm1))
+                e2 = e2 + a2
+                e2 = e2 + ff(L0.ff2, fast_layer_norm(e2, L0.ff_norm2))
+            else:
+                e1, e2 = a1, a2
+            for layer in layers[1:]:                 # rows are per pair from here on: the batch's own varlen path
+                e1, e2, _ = layer.forward_varlen(e1, e2, optr1, optr2)
+            out.append(self._pair_affinity(self._pool_rows(e1, b1, optr1), self._pool_rows(e2, b2, optr2)))
+        return out[0] if len(out) == 1 else torch.cat(out)
 
     @staticmethod
     def _make_lins_from_depth(depth, in_dim, scale_factor=2, include_norms=None):
