@@ -87,16 +87,35 @@ void* current_stream(const at::Tensor& t) { return (void*)c10::hip::getCurrentHI
 // backward pass is a plain `loss.backward()` -- ACCUMULATE mode (no `inputs=`, not torch.autograd.grad) -- and no leaf
 // carries a hook, a pass's node does what the 60 AccumulateGrad tasks would do, itself: p.grad = view of the gradient
 // arena (or p.grad += view when a gradient is already there), and takes its edges to those AccumulateGrad nodes out of
-// THIS backward (the engine skips invalid edges); an end-of-backward callback puts them back, so the graph is what it was:
-// torch.autograd.grad, backward(inputs=...), hooks (DDP, register_hook, post-accumulate hooks) and retain_graph see the
-// stock structure and take the stock path.  CGVP_EXACT_LEAVES=1 (or set_exact_leaves(True)) forces the stock path.
+// THIS backward (the engine skips invalid edges); an end-of-backward callback puts them back (ParkedEdges: also when the
+// backward fails), so the graph is what it was: torch.autograd.grad, backward(inputs=...), hooks (DDP, register_hook,
+// post-accumulate hooks) and retain_graph see the stock structure and take the stock path, and so does a pass in which
+// a leaf has another producer.  CGVP_EXACT_LEAVES=1 (or set_exact_leaves(True)) forces the stock path.
 bool g_exact_leaves = std::getenv("CGVP_EXACT_LEAVES") != nullptr && std::getenv("CGVP_EXACT_LEAVES")[0] == '1';
 long g_fast_leaf_passes = 0;                // diagnostics (tests): passes that took the fast path
+
+// The leaf edges a fast pass took out of its node, until they are back.  The end-of-backward callback of that pass owns
+// the only strong reference, so they return when the callback runs AND when it is destroyed without having run: the engine
+// skips the final callbacks of a backward in which a later node threw, and destroys them with that backward's graph task
+// while backward() unwinds.  Without this a graph kept with retain_graph=True would lose its leaves for
+// good after one failed pass.  The node keeps a weak reference and restores them itself when it is entered next.
+struct ParkedEdges {
+  std::shared_ptr<Node> node;           // (keeps the node alive while its edges are here)
+  torch::autograd::edge_list edges;     // edges [0, edges.size()) of `node`
+  void restore() {
+    if (!node) return;
+    for (size_t i = 0; i < edges.size(); ++i) node->next_edges()[i] = std::move(edges[i]);
+    edges.clear();
+    node.reset();
+  }
+  ~ParkedEdges() { restore(); }
+};
 
 struct LeafScatter {
   // `views[i]`: the gradient of parameter i (a view of the pass's gradient arena `garena`, arena order), for i < np.
   // Returns true when the leaves' .grad hold the result: the caller then returns UNDEFINED outputs for [0, np).
-  static bool run(Node& node, size_t np, const std::vector<at::Tensor>& views, const at::Tensor& garena) {
+  static bool run(Node& node, std::weak_ptr<ParkedEdges>& parked, size_t np, const std::vector<at::Tensor>& views,
+                  const at::Tensor& garena) {
     if (g_exact_leaves || at::GradMode::is_enabled()) return false;
     const auto* exec_info = torch::autograd::get_current_graph_task_exec_info();
     if (exec_info && !exec_info->empty()) return false;          // autograd.grad / backward(inputs=...): captures needed
@@ -106,6 +125,13 @@ struct LeafScatter {
       if (!e.is_valid()) continue;                                // a frozen parameter
       auto* a = dynamic_cast<torch::autograd::AccumulateGrad*>(e.function.get());
       if (!a || e.input_nr != 0) return false;                    // not a leaf (a view / clone of one): stock path
+      // This node must be the leaf's ONLY producer.  The engine counted one dependency of the AccumulateGrad node per
+      // edge that leads to it before this backward started; taking our edge out leaves that count one short of zero,
+      // and the other producer's gradient (an L2 term on the parameter, a tied weight, a stock op that reads it) would
+      // wait in the engine's buffer for ever and be dropped without an error.  Edges own their target and the variable
+      // holds it weakly, so "no other edge anywhere" is one load per leaf: a second edge in ANOTHER live graph (or a
+      // Python reference to the accumulator) also sends this pass down the stock path, which is correct, only slower.
+      if (e.function.use_count() != 1) return false;
       if (!a->pre_hooks().empty() || !a->post_hooks().empty() || !a->tensor_pre_hooks().empty() ||
           !a->retains_grad_hooks().empty() || a->tensor_post_acc_grad_hooks() != nullptr)
         return false;                                             // somebody listens at this leaf: stock path
@@ -149,12 +175,14 @@ struct LeafScatter {
     }
     // Take the leaf edges out of this backward, and put them back when it ends.  Also what the engine does for leaf
     // streams: the caller's stream waits for the stream this node ran on, if that is another one.
-    auto self = node.getptr();
-    auto saved = std::make_shared<torch::autograd::edge_list>(node.next_edges().begin(), node.next_edges().begin() + np);
+    auto saved = std::make_shared<ParkedEdges>();
+    saved->node = node.getptr();
+    saved->edges.assign(node.next_edges().begin(), node.next_edges().begin() + np);
     for (size_t i = 0; i < np; ++i) node.next_edges()[i] = torch::autograd::Edge();
+    parked = saved;
     const c10::hip::HIPStream ran_on = c10::hip::getCurrentHIPStream(garena.device().index());
-    torch::autograd::Engine::get_default_engine().queue_callback([self, saved, np, ran_on]() {
-      for (size_t i = 0; i < np; ++i) self->next_edges()[i] = (*saved)[i];
+    torch::autograd::Engine::get_default_engine().queue_callback([saved, ran_on]() {
+      saved->restore();
       // (the callback runs on the thread that called backward(), with the caller's streams current)
       const c10::hip::HIPStream now = c10::hip::getCurrentHIPStream(ran_on.device_index());
       if (now != ran_on) {
@@ -304,10 +332,16 @@ struct EncoderBackward : public Node, PassSaved {
   bool need_x = false;
   bool one_leaf = false;            // the single leaf is the flat arena: it gets the arena itself, LeafScatter stays out
   std::vector<Guarded> guarded;
+  std::weak_ptr<ParkedEdges> parked;  // the leaf edges a fast pass took out, while its end-of-backward callback is pending
 
+  void unpark() {
+    if (auto p = parked.lock()) p->restore();
+    parked.reset();
+  }
   variable_list apply(variable_list&& grads) override {
     constexpr PassNames names = Pass::kNames;
     Tic tic_all(names.apply);
+    unpark();                         // (a pass that left them out has ended, however it ended)
     // The kernels' backward is not itself differentiable: create_graph=True must fail loudly instead of returning constants.
     TORCH_CHECK(!at::GradMode::is_enabled(), "caster_gvp: ", names.node, " is not differentiable twice (backward called "
                 "with create_graph=True); the encoder kernels provide first derivatives only");
@@ -339,13 +373,15 @@ struct EncoderBackward : public Node, PassSaved {
     } else {
       for (size_t i = 0; i < np; ++i)      // one view op per parameter (as_strided), not narrow + view
         if (task_should_compute_output(i)) out[i] = arena_view(garena, slots[i].sizes, slots[i].strides, slots[i].offset);
-      if (LeafScatter::run(*this, np, out, garena))
+      if (LeafScatter::run(*this, parked, np, out, garena))
         for (size_t i = 0; i < np; ++i) out[i] = at::Tensor();
     }
     if (need_x)
       for (size_t i = 0; i < ni; ++i) out[np + i] = pass.input_grad(g_in[i]);
     return out;
   }
+  // (not the place to unpark(): without retain_graph the engine calls this right after apply(), BEFORE it walks the next
+  // edges, and every leaf would get its engine task after all)
   void release_variables() override {
     ws.reset(); csr.clear(); guarded.clear();
     static_cast<Pass&>(*this).release_inputs();

@@ -22,6 +22,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import math
 import os
 
 import torch
@@ -60,16 +61,61 @@ class _Bucket:
         self.graph, self.out, self.steps = None, None, 0
 
 
+# The ten feature tensors of a batch: (dict, field, index in a tuple field or None, which of the bucket's four sizes
+# (residues, protein edges, atoms, drug edges) is its row capacity, its name in messages)
+_FEATURES = tuple((side, field, i, size, f"{'pdata' if side == 'p' else 'mdata'}[{field!r}]" + ("" if i is None else f"[{i}]"))
+                  for side, field, i, size in (("p", "x", 0, 0), ("p", "x", 1, 0), ("p", "ntypes", None, 0), ("p", "etypes", None, 1),
+                                               ("p", "eattr", 0, 1), ("p", "eattr", 1, 1), ("m", "x", None, 2),
+                                               ("m", "ntypes", None, 2), ("m", "etypes", None, 3), ("m", "eattr", None, 3)))
+
+
+def _field(d, field, i):
+    return d[field] if i is None else d[field][i]
+
+
 class _BucketedGraphs:
     """Capture-or-replay core of both steps.  A subclass supplies `_new_bucket`, `_pairs` (its staging pairs after the ten
-    feature tensors), `_step` and `_capture_mode` (the context of a bucket's creation, warm-up and capture)."""
+    feature tensors), `_exact` (name, source and required shape of each of those), `_step` and `_capture_mode` (the
+    context of a bucket's creation, warm-up and capture)."""
+
+    def _check_batch(self, key, b, pdata, mdata, *extra):
+        """The staging launch gets raw addresses and byte counts: a source on the host or on another GPU would be a device
+        read of a foreign address, a source larger than its static buffer a write past its end.  So everything `_stage`
+        will be given is checked here, on the host, before a bucket is created, staged or captured: ValueError.  `b` is
+        the batch's bucket, or None when this batch is about to create it (its trailing dimensions are then the
+        batch's own)."""
+        dev = self.device
+
+        def foreign(name, t):
+            if not isinstance(t, torch.Tensor):
+                return ValueError(f"{name}: expected a tensor, got {type(t).__name__}")
+            return ValueError(f"{name} is on {t.device}, the captured step's buffers are on {dev}: move the batch to the "
+                              "model's device first (.to(device, non_blocking=True))")
+        for side, field, i, size, name in _FEATURES:
+            src = _field(pdata if side == "p" else mdata, field, i)
+            if not isinstance(src, torch.Tensor) or src.device != dev:
+                raise foreign(name, src)
+            if src.dim() < 1 or src.shape[0] > key[size]:
+                raise ValueError(f"{name} has shape {tuple(src.shape)}: more than the {key[size]} rows of the batch's bucket")
+            if b is not None and src.shape[1:] != _field(getattr(b, side), field, i).shape[1:]:
+                raise ValueError(f"{name} has shape {tuple(src.shape)}, the captured step was built for rows of shape "
+                                 f"{tuple(_field(getattr(b, side), field, i).shape[1:])}")
+        for name, src, size in (("pdata['edge_index']", pdata["edge_index"], 1), ("mdata['edge_index']", mdata["edge_index"], 3)):
+            if not isinstance(src, torch.Tensor) or src.device != dev:
+                raise foreign(name, src)
+            if src.dim() != 2 or src.shape[0] != 2 or src.shape[1] > key[size]:
+                raise ValueError(f"{name} has shape {tuple(src.shape)}: expected [2, E] with E <= {key[size]}, the batch's bucket")
+        for name, src, shape in self._exact(key, b, pdata, mdata, *extra):
+            if not isinstance(src, torch.Tensor) or src.device != dev:
+                raise foreign(name, src)
+            if src.numel() != math.prod(shape) or (src.dim() and src.shape[0] != shape[0]):
+                raise ValueError(f"{name} has shape {tuple(src.shape)}, the captured step expects {tuple(shape)}")
 
     def _stage(self, b, pdata, mdata, extra):
-        """ONE launch copies the batch into b's static buffers; returns the sources that must outlive the copy."""
-        pairs = [(b.p["x"][0], pdata["x"][0]), (b.p["x"][1], pdata["x"][1]), (b.p["ntypes"], pdata["ntypes"]),
-                 (b.p["etypes"], pdata["etypes"]), (b.p["eattr"][0], pdata["eattr"][0]), (b.p["eattr"][1], pdata["eattr"][1]),
-                 (b.m["x"], mdata["x"]), (b.m["ntypes"], mdata["ntypes"]), (b.m["etypes"], mdata["etypes"]),
-                 (b.m["eattr"], mdata["eattr"])] + extra
+        """ONE launch copies the batch into b's static buffers; returns the sources that must outlive the copy.  (The
+        sources have passed `_check_batch`.)"""
+        pairs = [(_field(getattr(b, side), field, i), _field(pdata if side == "p" else mdata, field, i))
+                 for side, field, i, _, _ in _FEATURES] + extra
         items = (_lib.StageItem * _lib.MAX_STAGE)()
         keep, k = [], 0
         for dst, src in pairs:
@@ -95,6 +141,7 @@ class _BucketedGraphs:
         """Stage the batch and replay its bucket's graph (captured at the first visit); returns the bucket."""
         sdt = torch.bfloat16 if pdata["x"][0].dtype == torch.bfloat16 else torch.float32
         b = self.buckets.get(mode_key(key, sdt))
+        self._check_batch(key, b, pdata, mdata, *extra)
         if b is not None and b.graph is not None:
             # steady state: stage + replay on the caller's stream (a graph replays on whatever stream it is launched on;
             # no cross-stream dependency, which costs ~10 us of idle device per hop)
@@ -159,6 +206,11 @@ class GraphedEncoderStep(_BucketedGraphs):
     def _pairs(self, b, pdata, mdata, g_res, g_atm):
         return [(b.g_res, g_res), (b.g_atm, g_atm)] if self.train else []
 
+    def _exact(self, key, b, pdata, mdata, g_res, g_atm):
+        if not self.train:
+            return []
+        return [("g_res", g_res, (pdata["x"][0].shape[0], self.out_res)), ("g_atm", g_atm, (mdata["x"].shape[0], self.out_atm))]
+
     def _capture_mode(self):
         return torch.set_grad_enabled(self.train)
 
@@ -210,12 +262,26 @@ class GraphedTrainStep(_BucketedGraphs):
             loss, pred = step.run(pdata, mdata, y)                           # p.grad of every parameter is set
             optimizer.step()
 
+    `run` REPLACES every trainable parameter's .grad by this step's gradient: nothing is accumulated into a gradient that
+    is already there (unlike `loss.backward()`; no `zero_grad()` is needed between steps), and a parameter the step does
+    not use gets .grad = None, so a stale gradient of an earlier eager step is never applied again.
+
     With `optimizer=` a gvp_hip.optim.FusedAdam over `model.parameters()`, the update (unscale, clip, Adam, and the
     scaler's update when `scaler` is given: train_model.py:578-587) is part of the captured step: `run` still returns
     (loss, pred) and publishes p.grad, and the caller calls neither `optimizer.step()` nor `scaler.update()`.  The optimizer
     state is shared by all buckets, only the gradient addresses are per bucket; the warm-up passes of a capture run the
     update dry.  The learning rate is read from `param_groups[0]["lr"]` at every `run`; the other hyperparameters are those
-    of the construction.  Not together with `enable_pair_parallel` (the all-reduce sits between backward and update).
+    of the construction.
+
+    Row-wise heads only.  The step runs the head on B + 1 rows (below), and a capture runs it three times.  So a model
+    whose head mixes rows is refused with a RuntimeError, at construction and at `run`, before any bucket exists:
+    BatchNorm on batch statistics (out_lin_norm_type="batch" in training mode; in eval mode it normalises by the running
+    statistics, row by row, and is captured like any other head), and `enable_pair_parallel()` with or without
+    `optimizer=` (the gather would carry the padding pair, and the all-reduce sits between backward and update).
+
+    The batch must be on the model's device: `run` raises ValueError for a tensor that is on the host or another GPU
+    (`y` straight from a loader), for `ptr` or `target` that do not hold B + 1 / B entries, and for a feature tensor whose
+    trailing dimensions differ from the bucket's -- before anything is staged.
 
     With `meter=` a gvp_hip.metrics.RegressionMeter on the model's device, every `run` appends its B predictions and
     targets to the meter inside the captured step (the warm-up passes of a capture add nothing, the padding pair is never
@@ -245,7 +311,6 @@ class GraphedTrainStep(_BucketedGraphs):
             if not isinstance(optimizer, FusedAdam):
                 raise TypeError(f"GraphedTrainStep(optimizer=...) captures a gvp_hip.optim.FusedAdam, not a {type(optimizer).__name__}: "
                                 "step any other optimizer after `run`, from the published p.grad")
-            self._check_not_pair_parallel()
             slot = {id(p): i for i, p in enumerate(optimizer.param_groups[0]["params"])}
             if any(id(p) not in slot for p in self.params):
                 raise ValueError("GraphedTrainStep(optimizer=...): the optimizer must hold every trainable parameter of the model "
@@ -258,11 +323,24 @@ class GraphedTrainStep(_BucketedGraphs):
                 raise TypeError(f"GraphedTrainStep(meter=...) captures a gvp_hip.metrics.RegressionMeter, not a {type(meter).__name__}")
             if meter.device != self.device:
                 raise ValueError(f"GraphedTrainStep(meter=...): the meter lives on {meter.device}, the model on {self.device}")
+        self._batch_norms = [(n, m) for n, m in model.named_modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)]
+        self._check_row_wise()
 
-    def _check_not_pair_parallel(self):
+    def _check_row_wise(self):
+        """The captured step runs the head on B + 1 rows (the padding pair) and twice more to warm up: refuse what is not
+        row-wise.  At construction and at every `run` (a mode can change in between), before a bucket exists."""
         if getattr(self.model, "_pair_parallel", False):
-            raise RuntimeError("GraphedTrainStep(optimizer=...) cannot be combined with enable_pair_parallel(): the gradient "
-                               "all-reduce belongs between the backward pass and the update")
+            raise RuntimeError("GraphedTrainStep cannot be combined with enable_pair_parallel(): the captured step carries a "
+                               "padding pair that the gather would send to every rank as one of the local pairs"
+                               + ("" if self.optimizer is None else ", and the gradient all-reduce belongs between the "
+                                  "backward pass and the captured update"))
+        for name, mod in self._batch_norms:
+            if mod.training or mod.running_mean is None:
+                raise RuntimeError(f"GraphedTrainStep cannot run BatchNorm on batch statistics ({name or 'the model'}, "
+                                   "out_lin_norm_type='batch' in training mode): the padding pair of the captured step would "
+                                   "enter the mean and variance of every real pair, and the warm-up passes of a capture would "
+                                   "advance the running statistics.  Use the eager step, out_lin_norm_type='layer', or "
+                                   "model.eval() (running statistics are row-wise)")
 
     def _new_bucket(self, key, sdt, pdata, mdata, target):
         N, E, Na, Ea, B = key
@@ -278,6 +356,11 @@ class GraphedTrainStep(_BucketedGraphs):
 
     def _pairs(self, b, pdata, mdata, target):
         return [(b.target, target), (b.p["ptr"][:-1], pdata["ptr"]), (b.m["ptr"][:-1], mdata["ptr"])]   # (the last offset stays the padded size)
+
+    def _exact(self, key, b, pdata, mdata, target):
+        B = key[4]
+        rest = tuple(b.target.shape[1:]) if b is not None else tuple(target.shape[1:]) if isinstance(target, torch.Tensor) else ()
+        return [("target", target, (B,) + rest), ("pdata['ptr']", pdata["ptr"], (B + 1,)), ("mdata['ptr']", mdata["ptr"], (B + 1,))]
 
     @contextlib.contextmanager
     def _capture_mode(self):
@@ -326,8 +409,8 @@ class GraphedTrainStep(_BucketedGraphs):
 
     def _publish(self, b):
         loss, pred, grads = b.out
-        for p, g in zip(self.params, grads):
-            if g is not None and p.grad is not g:
+        for p, g in zip(self.params, grads):        # (g None: a parameter the step does not use loses a stale gradient)
+            if p.grad is not g:
                 p.grad = g
         return loss, pred
 
@@ -338,8 +421,8 @@ class GraphedTrainStep(_BucketedGraphs):
         Na, Ea = mdata["x"].shape[0], mdata["edge_index"].shape[1]
         B = int(pdata["ptr"].numel()) - 1
         key = (self.quantum(N + 1), self.quantum(E), self.quantum(Na + 1), self.quantum(Ea), B)
+        self._check_row_wise()
         if self.optimizer is not None:
-            self._check_not_pair_parallel()
             if self.optimizer.hyper_key() != self._opt_key:
                 raise RuntimeError("the optimizer's betas / eps / weight decay / max_grad_norm changed since GraphedTrainStep was "
                                    "built: captured steps keep the old values (only the learning rate is read at run time)")
