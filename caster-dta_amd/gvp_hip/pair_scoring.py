@@ -208,6 +208,10 @@ def _(q1, k1, v1, q2, k2, v2, ptr1, ptr2, g1, g2, optr1, optr2, heads, rows1=-1,
 def expand_rows_op(src: Tensor, src_ptr: Tensor, g: Tensor, optr: Tensor, num_out: int) -> Tuple[Tensor, Tensor]:
     """-> (rows [num_out, W] with rows[optr[b] + r] = src[src_ptr[g[b]] + r], batch [num_out] int64 with
     batch[optr[b] + r] = b).  W is a multiple of 4; num_out is optr[-1] as the host knows it (`plan_pairs`)."""
+    return _expand(src, src_ptr, g, optr, num_out)
+
+
+def _expand(src, src_ptr, g, optr, num_out):
     _on_gpu(src, "src")
     if src.dim() != 2 or src.shape[1] < 4 or src.shape[1] % 4:
         raise NotImplementedError(f"src: expected [rows, W] with W a multiple of 4, got {tuple(src.shape)}")

@@ -478,19 +478,37 @@ class JointGNN(nn.Module):
         `enable_pair_parallel`.  Attention weights and node scores are not produced; `attention_weights`,
         `node_attention` and `last_node_attention` are left as they are."""
         from gvp_hip import pair_scoring as ps
+        dev, ptr1, ptr2 = self._unique_graph_inputs("score_pairs", protein_graph_data, molecule_graph_data)
+        len1, len2, pairs = self._read_pair_tables(ptr1, ptr2, pairs)
+        chunks = ps.plan_pairs(len1, len2, pairs, max_rows)          # IndexError here, before the first launch
+        was_training = self.training
+        self.eval()
+        try:
+            return self._score_chunks(protein_graph_data, molecule_graph_data, ptr1, ptr2, chunks, dev)
+        finally:
+            self.train(was_training)
+
+    def _unique_graph_inputs(self, what, protein_graph_data, molecule_graph_data):
+        """What every pair-list entry point asks of its two batches of unique graphs -> (device, ptr1, ptr2).
+        NotImplementedError, never a dense fallback: CPU tensors, `enable_pair_parallel`, a head shape
+        `varlen_supported` refuses."""
         xs = [d.get("x", None) for d in (protein_graph_data, molecule_graph_data)]
         xs = [x[0] if isinstance(x, (tuple, list)) else x for x in xs]
         if not all(torch.is_tensor(x) and x.is_cuda for x in xs):
-            raise NotImplementedError("score_pairs runs on MI355X only: both graph dicts must hold CUDA tensors")
+            raise NotImplementedError(f"{what} runs on MI355X only: both graph dicts must hold CUDA tensors")
         if self._pair_parallel:
-            raise NotImplementedError("score_pairs does not shard pairs over ranks (enable_pair_parallel is on)")
-        dev = xs[0].device
+            raise NotImplementedError(f"{what} does not shard pairs over ranks (enable_pair_parallel is on)")
         cam = self.cross_attn_module
         if cam is not None and not cam.varlen_supported(xs[0]):
-            raise NotImplementedError("score_pairs needs head shapes the varlen attention kernels are compiled for "
+            raise NotImplementedError(f"{what} needs head shapes the varlen attention kernels are compiled for "
                                       "(head_dim 16, 32 or 64 in both directions, one head count)")
         ptr1, ptr2 = (self._unique_ptr(d, x) for d, x in zip((protein_graph_data, molecule_graph_data), xs))
-        # the one host read: both ptr tables and, when it lives on the device, the pair list
+        return xs[0].device, ptr1, ptr2
+
+    @staticmethod
+    def _read_pair_tables(ptr1, ptr2, pairs):
+        """The one host read of a pair-list call: both ptr tables and, when it lives on the device, the pair list
+        -> (len1, len2, pairs) on the host."""
         on_dev = torch.is_tensor(pairs) and pairs.is_cuda
         flat = torch.cat([ptr1, ptr2] + ([pairs.reshape(-1).to(torch.int64)] if on_dev else [])).cpu().numpy()
         n1, n2 = ptr1.numel(), ptr2.numel()
@@ -499,13 +517,128 @@ class JointGNN(nn.Module):
             pairs = flat[n1 + n2:].reshape(-1, 2)
         elif torch.is_tensor(pairs):
             pairs = pairs.numpy()
-        chunks = ps.plan_pairs(len1, len2, pairs, max_rows)          # IndexError here, before the first launch
-        was_training = self.training
-        self.eval()
-        try:
-            return self._score_chunks(protein_graph_data, molecule_graph_data, ptr1, ptr2, chunks, dev)
-        finally:
-            self.train(was_training)
+        return len1, len2, pairs
+
+    @staticmethod
+    def _first_layer_projections(L0, residue, atom):
+        """Everything of the first cross-attention layer that does not depend on the partner, once per unique graph: the
+        pre-attention LayerNorms and the Q / K / V projections -> (q1, k1, v1, q2, k2, v2)."""
+        from gvp_hip.head_ops import fast_layer_norm
+        E1, E2 = L0.embed1_to_2.embed_dim, L0.embed2_to_1.embed_dim
+        p12, p21 = L0._proj_parts(L0.embed1_to_2), L0._proj_parts(L0.embed2_to_1)
+        n1 = fast_layer_norm(residue, L0.preattn_norm1)
+        q1 = L0._q(p12, n1)
+        k2, v2 = L0._kv(p21, n1, E2)
+        n2 = fast_layer_norm(atom, L0.preattn_norm2)
+        q2 = L0._q(p21, n2)
+        k1, v1 = L0._kv(p12, n2, E1)
+        return q1, k1, v1, q2, k2, v2
+
+    # ------------------------------------------------------------ pair lists over unique graphs (training)
+    def forward_pairs(self, protein_graph_data, molecule_graph_data, pairs=None):
+        """`forward` on a LIST OF PAIRS drawn from P unique proteins and D unique molecules, each encoded once, under
+        autograd -> (prediction [K, 1], None).
+
+        The two dicts and `pairs` are those of `score_pairs`; `pairs` may also be a ready
+        `gvp_hip.pair_training.PairTrainPlan` (`plan_pair_training(len1, len2, pairs)`).  A training batch drawn as a
+        block -- 8 proteins x 8 drugs = 64 pairs -- runs both encoders, the residue / atom stacks and the first
+        cross-attention layer's LayerNorms and projections on 8 + 8 graphs instead of 64 + 64; the attention core reads
+        the unique rows through the pair tables (caster_gvp::cross_attention_pairs_train), the residual stream starts
+        from their per-pair copy (caster_gvp::expand_rows_train), and the backward of both sums, for every unique graph,
+        the gradients of the pairs that reference it in ascending pair order -- no float atomics, bitwise reproducible.
+        All K pairs are one chunk.
+
+        The module's mode is honoured and left alone (no eval(), no no_grad).  Dropout in training mode: every site
+        BEFORE the pairing (both encoders, the residue / atom stacks; without a cross-attention layer also the protein /
+        molecule stacks) is drawn once per unique graph and shared by all its pairs -- a collated batch draws it per
+        copy; every site AFTER the pairing is drawn per pair.  In eval mode the result is that of `forward` on the
+        collated pairs (and of `score_pairs`).
+
+        Host contract: `ptr` of both sides and a device-resident `pairs` are read to the host ONCE; with a
+        PairTrainPlan nothing is read.  An index outside 0 .. P-1 / 0 .. D-1 raises IndexError before the first launch.
+        NotImplementedError, never a dense fallback: CPU tensors, a head shape `varlen_supported` refuses,
+        `enable_pair_parallel`, and attention_dropout > 0 in training mode (the pair kernels draw no dropout).  Attention
+        weights and node scores are not produced."""
+        from gvp_hip import pair_training as pt
+        dev, ptr1, ptr2 = self._unique_graph_inputs("forward_pairs", protein_graph_data, molecule_graph_data)
+        cam = self.cross_attn_module
+        if cam is not None and self.training and any(float(m.dropout) > 0 for layer in cam.cross_attn_layers[:1]
+                                                     for m in (layer.embed1_to_2, layer.embed2_to_1)):
+            raise NotImplementedError("forward_pairs: attention dropout in training mode is not implemented on pair "
+                                      "tables (attention_dropout > 0); use forward() on the collated batch")
+        if isinstance(pairs, pt.PairTrainPlan):
+            plan = pairs
+        else:
+            plan = pt.plan_pair_training(*self._read_pair_tables(ptr1, ptr2, pairs))    # IndexError before any launch
+        return self._train_pairs(protein_graph_data, molecule_graph_data, ptr1, ptr2, plan, dev), None
+
+    def _train_pairs(self, protein_graph_data, molecule_graph_data, ptr1, ptr2, plan, dev):
+        """`_score_chunks` for one chunk, differentiable, with the dropout sites of `head`."""
+        from gvp_hip import pair_training as pt
+        from gvp_hip.head_ops import DropSites, fast_layer_norm, fast_linear
+        hdt = self.output_layer.weight.dtype
+        if plan.g1.shape[0] == 0:
+            return torch.empty(0, 1, dtype=hdt, device=dev)
+        # ---- once per unique graph
+        residue = self.protein_gnn(**{k: v for k, v in protein_graph_data.items() if k != "ptr"})
+        atom = self.molecule_gnn(**{k: v for k, v in molecule_graph_data.items() if k != "ptr"})
+        if not torch.is_autocast_enabled():
+            residue, atom = residue.to(hdt), atom.to(hdt)
+        sites = DropSites(residue, self.training, self.dropout.p)
+        residue = self._stack(residue, self.residue_lins, self.residue_norms, sites)
+        atom = self._stack(atom, self.atom_lins, self.atom_norms, sites)
+        t = plan.on(dev)                             # one upload per plan: a ready plan brings its tables along
+
+        def pooled_stack(pooled, side):              # `_pooled_stack` with the fused dropout sites
+            norm, lins, norms = ((self.protein_post_pool_norm if self.include_post_pool_layernorm else None,
+                                  self.protein_lins, self.protein_norms) if side == 1 else
+                                 (self.molecule_post_pool_norm if self.include_post_pool_layernorm else None,
+                                  self.molecule_lins, self.molecule_norms))
+            if norm is not None:
+                pooled = norm(pooled)
+            return self._stack(sites.act_dropout(pooled, self.activation, self.dropout), lins, norms, sites)
+
+        def embed_pairs(protein, molecule):
+            z = sites.act_dropout(self.pm_embed_lin(torch.cat([protein, molecule], dim=-1)), self.activation, self.dropout)
+            return self.output_layer(self._stack(z, self.out_fc_layers, self.out_fc_norms, sites))
+
+        if self.cross_attn_module is None:
+            # nothing depends on the partner before the pair embedding: pool and stack the unique graphs, index per pair
+            # (index_select's own backward does the sum)
+            b1 = torch.repeat_interleave(torch.arange(ptr1.numel() - 1, device=dev), ptr1[1:] - ptr1[:-1],
+                                         output_size=residue.shape[0])
+            b2 = torch.repeat_interleave(torch.arange(ptr2.numel() - 1, device=dev), ptr2[1:] - ptr2[:-1],
+                                         output_size=atom.shape[0])
+            protein = pooled_stack(self._pool_rows(residue, b1, ptr1), 1)
+            molecule = pooled_stack(self._pool_rows(atom, b2, ptr2), 2)
+            return embed_pairs(protein.index_select(0, t["g1"]), molecule.index_select(0, t["g2"]))
+        layers = list(self.cross_attn_module.cross_attn_layers)
+        L0 = layers[0]
+        q1, k1, v1, q2, k2, v2 = self._first_layer_projections(L0, residue, atom)
+        heads = L0.embed1_to_2.num_heads
+        # ---- per pair: only what depends on the partner
+        o1, o2 = pt.cross_attention_pairs_train(q1, k1, v1, q2, k2, v2, ptr1, ptr2, t["g1"], t["g2"], t["optr1"], t["optr2"],
+                                                t["inv1_ptr"], t["inv1_pairs"], t["inv2_ptr"], t["inv2_pairs"], heads,
+                                                plan.rows1, plan.rows2)
+        a1 = fast_linear(o1, L0.embed1_to_2.out_proj.weight, L0.embed1_to_2.out_proj.bias)
+        a2 = fast_linear(o2, L0.embed2_to_1.out_proj.weight, L0.embed2_to_1.out_proj.bias)
+        e1, b1 = pt.expand_rows_train(residue, ptr1, t["g1"], t["optr1"], t["inv1_ptr"], t["inv1_pairs"], plan.rows1)
+        e2, b2 = pt.expand_rows_train(atom, ptr2, t["g2"], t["optr2"], t["inv2_ptr"], t["inv2_pairs"], plan.rows2)
+        if L0.include_residual_stream:
+            def ff(seq, x):          # nn.Sequential(Linear, ReLU, Dropout, Linear), as forward_varlen runs it
+                h = sites.act_dropout(fast_linear(x, seq[0].weight, seq[0].bias), seq[1], seq[2])
+                return fast_linear(h, seq[3].weight, seq[3].bias)
+            e1 = sites.dropout_add(e1, a1, L0.ff_dropout)
+            e1 = sites.dropout_add(e1, ff(L0.ff1, fast_layer_norm(e1, L0.ff_norm1)), L0.ff_dropout)
+            e2 = sites.dropout_add(e2, a2, L0.ff_dropout)
+            e2 = sites.dropout_add(e2, ff(L0.ff2, fast_layer_norm(e2, L0.ff_norm2)), L0.ff_dropout)
+        else:
+            e1, e2 = a1, a2
+        for layer in layers[1:]:                     # rows are per pair from here on: the batch's own varlen path
+            e1, e2, _ = layer.forward_varlen(e1, e2, t["optr1"], t["optr2"], False, sites)
+        protein = pooled_stack(self._pool_rows(e1, b1, t["optr1"]), 1)
+        molecule = pooled_stack(self._pool_rows(e2, b2, t["optr2"]), 2)
+        return embed_pairs(protein, molecule)
 
     @staticmethod
     def _unique_ptr(data, x):
@@ -568,14 +701,7 @@ class JointGNN(nn.Module):
             return self._embed_pairs(protein.index_select(0, g1), molecule.index_select(0, g2))
         layers = list(self.cross_attn_module.cross_attn_layers)
         L0 = layers[0]
-        E1, E2 = L0.embed1_to_2.embed_dim, L0.embed2_to_1.embed_dim
-        p12, p21 = L0._proj_parts(L0.embed1_to_2), L0._proj_parts(L0.embed2_to_1)
-        n1 = fast_layer_norm(residue, L0.preattn_norm1)
-        q1 = L0._q(p12, n1)
-        k2, v2 = L0._kv(p21, n1, E2)
-        n2 = fast_layer_norm(atom, L0.preattn_norm2)
-        q2 = L0._q(p21, n2)
-        k1, v1 = L0._kv(p12, n2, E1)
+        q1, k1, v1, q2, k2, v2 = self._first_layer_projections(L0, residue, atom)
         heads = L0.embed1_to_2.num_heads
 
         def ff(seq, t):              # nn.Sequential(Linear, ReLU, Dropout, Linear) in eval mode
