@@ -11,6 +11,7 @@ SRCS=(gvp_kernels graph_index_kernels gvp_quad_kernels gvp_quad_bwd_kernels gine
 [ -f "$HERE/attn_score_kernels.hip" ] && SRCS+=(attn_score_kernels)
 [ -f "$HERE/attn_pairs_kernels.hip" ] && SRCS+=(attn_pairs_kernels)
 [ -f "$HERE/attn_pairs_bwd_kernels.hip" ] && SRCS+=(attn_pairs_bwd_kernels)
+[ -f "$HERE/attn_pairs_score_kernels.hip" ] && SRCS+=(attn_pairs_score_kernels)
 [ -f "$HERE/feat_kernels.hip" ] && SRCS+=(feat_kernels)
 [ -f "$HERE/structure_kernels.hip" ] && SRCS+=(structure_kernels)
 [ -f "$HERE/optim_kernels.hip" ] && SRCS+=(optim_kernels)

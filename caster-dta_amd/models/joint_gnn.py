@@ -76,6 +76,34 @@ def _dense_node_attention(w1, w2, mask1, mask2):
     return NodeAttention(residue_mean, residue_max, atom_mean, atom_max)
 
 
+# Row-wise ops whose result for a row does not depend on HOW MANY rows the call holds.  The library GEMM behind F.linear
+# picks its kernel (and with it the order of a row's sum) from the row count, and `fast_layer_norm` changes kernels at 256
+# rows, so per-pair rows computed chunk by chunk differ in the last bits from chunking to chunking.  The node scores of
+# `score_pairs_with_node_attention` must not: their later layers run on these.
+_INVARIANT_ROWS = 16384
+
+
+def _rows_linear(x, weight, bias):
+    """F.linear(x, weight, bias) as GEMMs of exactly `_INVARIANT_ROWS` rows each (the last block zero-padded): one problem
+    shape, hence one kernel, whatever x.shape[0] is; a row's result depends on that row and the weights alone."""
+    R = x.shape[0]
+    blocks = max(1, -(-R // _INVARIANT_ROWS))
+    padded = x.new_zeros(blocks * _INVARIANT_ROWS, x.shape[1])
+    padded[:R] = x
+    out = [torch.nn.functional.linear(b, weight, bias) for b in padded.split(_INVARIANT_ROWS)]
+    return (out[0] if blocks == 1 else torch.cat(out))[:R]
+
+
+def _rows_layer_norm(x, norm):
+    """`norm(x)` on the library's one-wave-per-row kernel at every row count (the widths it is compiled for), else the
+    module itself."""
+    if x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and x.shape[1] in (64, 128, 256, 512) and x.shape[0] > 0 \
+            and norm.elementwise_affine and norm.bias is not None and norm.weight.dtype == torch.float32:
+        from gvp_hip import head_ops  # noqa: F401  (registers the op)
+        return torch.ops.caster_gvp.layer_norm(x, norm.weight, norm.bias, float(norm.eps))[0]
+    return norm(x)
+
+
 class _BatchNorm(nn.Module):
     """Key-compatible stand-in for pyg.nn.BatchNorm (parameters live under `.module`)."""
 
@@ -475,8 +503,9 @@ class JointGNN(nn.Module):
         Contract: eval mode under no_grad (the training flag is restored); `ptr` of both sides and `pairs` are read to the
         host ONCE, the call's only synchronisation; an index outside 0 .. P-1 / 0 .. D-1 raises IndexError before anything
         is launched.  NotImplementedError, never a dense fallback: CPU tensors, a head shape `varlen_supported` refuses,
-        `enable_pair_parallel`.  Attention weights and node scores are not produced; `attention_weights`,
-        `node_attention` and `last_node_attention` are left as they are."""
+        `enable_pair_parallel`.  Attention weights and node scores are not produced (the node scores:
+        `score_pairs_with_node_attention`); `attention_weights`, `node_attention` and `last_node_attention` are left as
+        they are."""
         from gvp_hip import pair_scoring as ps
         dev, ptr1, ptr2 = self._unique_graph_inputs("score_pairs", protein_graph_data, molecule_graph_data)
         len1, len2, pairs = self._read_pair_tables(ptr1, ptr2, pairs)
@@ -487,6 +516,63 @@ class JointGNN(nn.Module):
             return self._score_chunks(protein_graph_data, molecule_graph_data, ptr1, ptr2, chunks, dev)
         finally:
             self.train(was_training)
+
+    @torch.no_grad()
+    def score_pairs_with_node_attention(self, protein_graph_data, molecule_graph_data, pairs=None, max_rows=262144):
+        """`score_pairs` that also returns the four per-node attention vectors of every pair
+        -> (affinity [K, 1], [NodeAttention per cross-attention layer], (optr1, optr2)).
+
+        The batches, `pairs`, the chunking, the single host read and the refusals are those of `score_pairs`, and so
+        are the affinities.  Each NodeAttention vector is compact over the PER-PAIR rows, in pair order (the chunks
+        concatenated): `residue_mean` / `residue_max` hold sum_b len1[g1[b]] entries, `atom_mean` / `atom_max`
+        sum_b len2[g2[b]].  optr1 / optr2 are the [K + 1] int64 offsets of the pairs in them, HOST tensors (the plan
+        knows them): `gvp_hip.attention_scores.per_pair(values, optr1)` gives the reference's list-of-arrays columns
+        without a device read.  The first layer's scores come from caster_gvp::cross_attention_pairs_node_scores on the
+        rows of the unique graphs (no per-pair copy of Q / K).  Later layers' scores come from a second pass over the
+        chunk's per-pair rows on row-count invariant ops (`_rows_linear`, `_rows_layer_norm`), so every vector is bitwise
+        the same whatever `max_rows` is; a model with one cross-attention layer (the shipped one) has no second pass.
+        K = 0 gives empty vectors for every layer.
+
+        RuntimeError: a model without a cross-attention layer (as `predict_with_node_attention`).  NotImplementedError
+        before the first launch, never the dense reduction with its host reads: a cross-attention layer wider than
+        `gvp_hip.attention_scores.MAX_WIDTH`.  Eval mode under no_grad (the training flag is restored);
+        `attention_weights`, `node_attention` and `last_node_attention` are left as they are."""
+        from gvp_hip import attention_scores, pair_scoring as ps
+        cam = self.cross_attn_module
+        if cam is None:
+            raise RuntimeError("score_pairs_with_node_attention: the model has no cross-attention layer")
+        dev, ptr1, ptr2 = self._unique_graph_inputs("score_pairs_with_node_attention", protein_graph_data,
+                                                    molecule_graph_data)
+        layers = list(cam.cross_attn_layers)
+        for layer in layers:
+            if max(layer.embed1_to_2.embed_dim, layer.embed2_to_1.embed_dim) > attention_scores.MAX_WIDTH:
+                raise NotImplementedError("score_pairs_with_node_attention: the attention-score kernels are compiled for "
+                                          f"embed widths up to {attention_scores.MAX_WIDTH}, got "
+                                          f"{layer.embed1_to_2.embed_dim} / {layer.embed2_to_1.embed_dim}")
+        len1, len2, pairs = self._read_pair_tables(ptr1, ptr2, pairs)
+        chunks = ps.plan_pairs(len1, len2, pairs, max_rows)          # IndexError here, before the first launch
+
+        def offsets(side):           # the chunks' own offsets, each shifted by the rows of the chunks before it
+            at, parts = 0, [np.zeros(1, dtype=np.int64)]
+            for c in chunks:
+                parts.append(getattr(c, f"optr{side}")[1:] + at)
+                at += getattr(c, f"rows{side}")
+            return torch.from_numpy(np.concatenate(parts))
+
+        optr = (offsets(1), offsets(2))
+        was_training = self.training
+        self.eval()
+        try:
+            per_chunk = []
+            affinity = self._score_chunks(protein_graph_data, molecule_graph_data, ptr1, ptr2, chunks, dev, per_chunk)
+        finally:
+            self.train(was_training)
+        if not per_chunk:
+            z = lambda: torch.empty(0, dtype=torch.float32, device=dev)
+            return affinity, [NodeAttention(z(), z(), z(), z()) for _ in layers], optr
+        scores = [per_chunk[0][i] if len(per_chunk) == 1 else
+                  NodeAttention(*(torch.cat([c[i][f] for c in per_chunk]) for f in range(4))) for i in range(len(layers))]
+        return affinity, scores, optr
 
     def _unique_graph_inputs(self, what, protein_graph_data, molecule_graph_data):
         """What every pair-list entry point asks of its two batches of unique graphs -> (device, ptr1, ptr2).
@@ -671,7 +757,10 @@ class JointGNN(nn.Module):
         z = self.dropout(self.activation(self.pm_embed_lin(torch.cat([protein, molecule], dim=-1))))
         return self.output_layer(self._stack(z, self.out_fc_layers, self.out_fc_norms))
 
-    def _score_chunks(self, protein_graph_data, molecule_graph_data, ptr1, ptr2, chunks, dev):
+    def _score_chunks(self, protein_graph_data, molecule_graph_data, ptr1, ptr2, chunks, dev, scores=None):
+        """Affinities [K, 1] of the planned chunks.  `scores`: a list that receives, per chunk, the list of its
+        NodeAttention per cross-attention layer (the first layer's from the pair tables, later layers' from a second,
+        row-count invariant pass over the per-pair rows); the affinities do not depend on it."""
         from gvp_hip import pair_scoring as ps
         from gvp_hip.head_ops import fast_layer_norm, fast_linear
         hdt = self.output_layer.weight.dtype
@@ -711,12 +800,30 @@ class JointGNN(nn.Module):
         # ---- per chunk: only what depends on the partner
         for i, c in enumerate(chunks):
             g1, g2, optr1, optr2 = views[4 * i:4 * i + 4]
-            o1, o2 = ps.cross_attention_pairs(q1, k1, v1, q2, k2, v2, ptr1, ptr2, g1, g2, optr1, optr2, heads,
-                                              c.rows1, c.rows2)
+            chunk_scores = None
+            if scores is None:
+                o1, o2 = ps.cross_attention_pairs(q1, k1, v1, q2, k2, v2, ptr1, ptr2, g1, g2, optr1, optr2, heads,
+                                                  c.rows1, c.rows2)
+            else:
+                from gvp_hip import pair_node_scores  # noqa: F401  (registers the op)
+                o1, o2, lse1, lse2 = ps.cross_attention_pairs(q1, k1, v1, q2, k2, v2, ptr1, ptr2, g1, g2, optr1, optr2,
+                                                              heads, c.rows1, c.rows2, lse=True)
+                atom_mean, atom_max, residue_mean, residue_max = torch.ops.caster_gvp.cross_attention_pairs_node_scores(
+                    q1, k1, lse1, q2, k2, lse2, ptr1, ptr2, g1, g2, optr1, optr2, heads)
+                chunk_scores = [NodeAttention(residue_mean, residue_max, atom_mean, atom_max)]
+                scores.append(chunk_scores)
             a1 = fast_linear(o1, L0.embed1_to_2.out_proj.weight, L0.embed1_to_2.out_proj.bias)
             a2 = fast_linear(o2, L0.embed2_to_1.out_proj.weight, L0.embed2_to_1.out_proj.bias)
             e1, b1 = ps.expand_rows(residue, ptr1, g1, optr1, c.rows1)      # the residual stream; b: the pooling's batch
             e2, b2 = ps.expand_rows(atom, ptr2, g2, optr2, c.rows2)
+            if chunk_scores is not None and len(layers) > 1:
+                # The later layers' scores come from a second pass over the chunk's per-pair rows on row-count invariant
+                # ops (`_rows_linear`, `_rows_layer_norm`): the pass below runs the library GEMMs at the chunk's row
+                # count, so its rows -- and scores taken from them -- would differ in the last bits from chunking to
+                # chunking.  The affinities stay on the pass below, bitwise those of `score_pairs`.
+                rows = L0.tail_rows_invariant(e1, e2, o1, o2)
+                for layer in layers[1:]:
+                    rows = layer.node_scores_rows_invariant(*rows, optr1, optr2, chunk_scores, last=layer is layers[-1])
             if L0.include_residual_stream:
                 e1 = e1 + a1
                 e1 = e1 + ff(L0.ff1, fast_layer_norm(e1, L0.ff_norm1))
@@ -933,6 +1040,48 @@ class CrossAttentionModule(nn.Module):
         else:
             embed_1, embed_2 = a1, a2
         return embed_1, embed_2, weights          # (embed_2 stays on the atom lane: the caller joins)
+
+    # ------------------------------------------------------------ the same layer, row-count invariant (eval mode, node scores)
+    def tail_rows_invariant(self, embed_1, embed_2, o1, o2):
+        """What follows the attention core in eval mode -- out-projection, residual stream, feed-forward -- on
+        `_rows_linear` / `_rows_layer_norm` -> (embed_1, embed_2)."""
+        a1 = _rows_linear(o1, self.embed1_to_2.out_proj.weight, self.embed1_to_2.out_proj.bias)
+        a2 = _rows_linear(o2, self.embed2_to_1.out_proj.weight, self.embed2_to_1.out_proj.bias)
+        if not self.include_residual_stream:
+            return a1, a2
+
+        def ff(seq, t):              # nn.Sequential(Linear, ReLU, Dropout, Linear) in eval mode
+            return _rows_linear(seq[1](_rows_linear(t, seq[0].weight, seq[0].bias)), seq[3].weight, seq[3].bias)
+
+        embed_1 = embed_1 + a1
+        embed_1 = embed_1 + ff(self.ff1, _rows_layer_norm(embed_1, self.ff_norm1))
+        embed_2 = embed_2 + a2
+        embed_2 = embed_2 + ff(self.ff2, _rows_layer_norm(embed_2, self.ff_norm2))
+        return embed_1, embed_2
+
+    def node_scores_rows_invariant(self, embed_1, embed_2, ptr1, ptr2, scores_out, last=False):
+        """`forward_varlen(..., scores_out=scores_out)` in eval mode with every row-wise op on `_rows_linear` /
+        `_rows_layer_norm`: the attention kernels work pair by pair, so the NodeAttention this appends does not depend
+        on which other pairs share the call.  -> (embed_1, embed_2) for the next layer, or None for the `last` one."""
+        from gvp_hip import attention_ops, attention_scores  # noqa: F401  (register the ops)
+        E1, E2 = self.embed1_to_2.embed_dim, self.embed2_to_1.embed_dim
+        p12, p21 = self._proj_parts(self.embed1_to_2), self._proj_parts(self.embed2_to_1)
+
+        def kv(parts, x, E):
+            if parts[2] is not None:
+                k, v = _rows_linear(x, parts[2], parts[3]).split([E, E], dim=1)
+                return k.contiguous(), v.contiguous()
+            return _rows_linear(x, parts[4], parts[5]), _rows_linear(x, parts[6], parts[7])
+
+        n1, n2 = _rows_layer_norm(embed_1, self.preattn_norm1), _rows_layer_norm(embed_2, self.preattn_norm2)
+        q1, q2 = _rows_linear(n1, p12[0], p12[1]), _rows_linear(n2, p21[0], p21[1])
+        (k2, v2), (k1, v1) = kv(p21, n1, E2), kv(p12, n2, E1)
+        heads = self.embed1_to_2.num_heads
+        o1, o2, lse1, lse2 = torch.ops.caster_gvp.cross_attention(q1, k1, v1, q2, k2, v2, ptr1, ptr2, heads)
+        atom_mean, atom_max, residue_mean, residue_max = torch.ops.caster_gvp.cross_attention_node_scores(
+            q1, k1, lse1, q2, k2, lse2, ptr1, ptr2, heads)
+        scores_out.append(NodeAttention(residue_mean, residue_max, atom_mean, atom_max))
+        return None if last else self.tail_rows_invariant(embed_1, embed_2, o1, o2)
 
     def forward(self, embed_1, embed_2, mask1, mask2, return_weights=True):
         n1, n2 = self.preattn_norm1(embed_1), self.preattn_norm2(embed_2)
