@@ -16,6 +16,7 @@ SRCS=(gvp_kernels graph_index_kernels gvp_quad_kernels gvp_quad_bwd_kernels gine
 [ -f "$HERE/structure_kernels.hip" ] && SRCS+=(structure_kernels)
 [ -f "$HERE/optim_kernels.hip" ] && SRCS+=(optim_kernels)
 [ -f "$HERE/metrics_kernels.hip" ] && SRCS+=(metrics_kernels)
+[ -f "$HERE/resident_kernels.hip" ] && SRCS+=(resident_kernels)
 [ -f "$HERE/linear_kernels.hip" ] && SRCS+=(linear_kernels)
 [ -f "$HERE/norm_kernels.hip" ] && SRCS+=(norm_kernels)
 [ -f "$HERE/elementwise_kernels.hip" ] && SRCS+=(elementwise_kernels)
