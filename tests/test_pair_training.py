@@ -253,7 +253,7 @@ def _pair_list():
     return pairs
 
 
-def _tables_of(pairs):
+def _tables_of(pairs, LEN1=LEN1, LEN2=LEN2):
     plan = pt.plan_pair_training(LEN1, LEN2, pairs)
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
     t = dict(pt.upload(plan, DEV), ptr1=dev(_ptr(LEN1)), ptr2=dev(_ptr(LEN2)), rows1=plan.rows1, rows2=plan.rows2, plan=plan)
@@ -300,7 +300,7 @@ def test_forward_is_the_inference_op_bitwise(tables, heads, w1, w2):
     assert got[0].requires_grad and got[1].requires_grad and torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
 
 
-def _dense_reference(ops, pairs, heads, g_o1, g_o2):
+def _dense_reference(ops, pairs, heads, g_o1, g_o2, LEN1=LEN1, LEN2=LEN2):
     """fp64, CPU: softmax attention per pair on index_select-ed rows of the unique graphs; autograd sums over the pairs."""
     leaves = [x.double().requires_grad_() for x in ops]
     q1, k1, v1, q2, k2, v2 = leaves
